@@ -7,7 +7,11 @@ re-launches itself that way as a child process. Per-GPU batch is fixed (weak sca
 region holds exactly K full training steps — device-side input conversion, forward, loss, backward
 with the bucketed all-reduce, and the fused optimizer update — bracketed by a barrier and
 ``torch.cuda.synchronize()``; the max over ranks is reported by rank 0 as one JSON line.
-Data: synthetic (random inputs + labels resident on each GPU); weights random-init.
+Data: synthetic (random inputs + labels resident on each GPU); weights random-init; both from fixed seeds, so the
+inputs are the same from run to run. A plain run sets up, warms up, times the K steps and prints the result line;
+``--dump-outputs DIR`` also writes the last timed step's loss and the weights it left as ``DIR/<name>.npy``;
+``--full`` adds the measurements and checks the headline figure does not need (replica checksum, single-step host
+issue time, all-reduce bus-bandwidth sweep for N>1).
 
 Other BASELINE.json configs: ``--model bert_base`` (seq 512, MultiWorkerMirroredStrategy, tokens/s),
 ``--model gpt2_medium_fp8`` (ctx 1024, fp8 projections, MirroredStrategy, tokens/s) and ``--model resnet50_ps``
@@ -116,7 +120,8 @@ def main():
                     help="1: capture the train step as per-stream hipGraphs (compile(jit_compile=True)), 0: eager; "
                          "default: per model from the interleaved A/B (profiles/r5_hipgraph_default.txt)")
     ap.add_argument("--ar-sweep", type=int, default=1,
-                    help="N>1: after the timed steps, time f32 all-reduces of 1-128 MB and report RCCL bus bandwidth")
+                    help="--full, N>1: after the timed steps, time f32 all-reduces of 1-128 MB and report RCCL bus "
+                         "bandwidth")
     ap.add_argument("--hiprio", type=int, default=None,
                     help="1: issue the train step on a high-priority HIP stream (the weight-gradient side stream keeps "
                          "normal priority, so the dgrad critical path wins block dispatch whenever a CU frees up); "
@@ -128,6 +133,13 @@ def main():
     ap.add_argument("--trainers", type=int, default=None, help="resnet50_ps: trainer tasks")
     ap.add_argument("--ps-cpu", action="store_true", help="resnet50_ps: PS shards in host shared memory")
     ap.add_argument("--ps-timeout", type=float, default=1500, help="resnet50_ps: whole-cluster time limit (s)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned and left behind as "
+                         "DIR/<name>.npy (float32): loss (the step's logs) and weights (the f32 master weights; a "
+                         "fixed, seeded sample of them when they exceed the size cap)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the replica checksum, the single-step host "
+                         "issue probe and, for N>1, the all-reduce bus-bandwidth sweep (see --ar-sweep)")
     args = ap.parse_args()
     if args.batch is None:
         args.batch = DEFAULT_BATCH[args.model]
@@ -198,30 +210,37 @@ def main():
         train_fn.check()  # a timed-out cross-stream wait of the graph replay fails the run (not a slow or wrong one)
     exposed = [b.exposed_ms() for b in bucketers if hasattr(b, "exposed_ms")]
     exposed = [e for e in exposed if e is not None]
-    # the loss and the replica checksum describe exactly the warmup + timed steps (taken before the probe below)
+    # the loss, the dumped outputs and the replica checksum describe exactly the warmup + timed steps (taken before
+    # the probe below)
     loss = float(logs["loss"])
-    # proof that the N replicas trained in lock step: an exact checksum of every trainable f32 master (the bit
-    # patterns summed as integers), compared across ranks (min == max); the world size the process group reports
     arena = getattr(model, "_arena", None)
-    csum = int(arena.flat.detach().view(torch.int32).to(torch.int64).sum().item()) if arena is not None else 0
-    # after the timed region: the host time to issue ONE step into an idle GPU queue (min of 3). In the timed loop
-    # the host is throttled by the queue once it runs ahead, so its issue time there equals the GPU time either way;
-    # this one says whether Python + launches alone would keep up with the GPU. (These 3 extra steps change the
-    # weights after the loss / checksum above were taken.)
-    single = []
-    for _ in range(3):
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        step()
-        single.append(time.perf_counter() - t1)
-    torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, loss, arena)
     rccl_world = dist.get_world_size() if dist.is_initialized() else 1
     backend = dist.get_backend() if dist.is_initialized() else None
-    identical = True
-    if dist.is_initialized():
-        mm = torch.tensor([csum, -csum], dtype=torch.int64, device=dev)
-        dist.all_reduce(mm, op=dist.ReduceOp.MAX)
-        identical = int(mm[0].item()) == csum and int(-mm[1].item()) == csum
+    extra = {}
+    if args.full:
+        # proof that the N replicas trained in lock step: an exact checksum of every trainable f32 master (the bit
+        # patterns summed as integers), compared across ranks (min == max)
+        csum = int(arena.flat.detach().view(torch.int32).to(torch.int64).sum().item()) if arena is not None else 0
+        # after the timed region: the host time to issue ONE step into an idle GPU queue (min of 3). In the timed
+        # loop the host is throttled by the queue once it runs ahead, so its issue time there equals the GPU time
+        # either way; this one says whether Python + launches alone would keep up with the GPU. (These 3 extra steps
+        # change the weights after the loss / dump / checksum above were taken.)
+        single = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            step()
+            single.append(time.perf_counter() - t1)
+        torch.cuda.synchronize()
+        identical = True
+        if dist.is_initialized():
+            mm = torch.tensor([csum, -csum], dtype=torch.int64, device=dev)
+            dist.all_reduce(mm, op=dist.ReduceOp.MAX)
+            identical = int(mm[0].item()) == csum and int(-mm[1].item()) == csum
+        extra = {"host_issue_ms_single_step": round(min(single) * 1e3, 3), "replicas_identical": identical,
+                 "weights_checksum": csum}
     t = torch.tensor([dt, sum(exposed) if exposed else 0.0], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)  # slowest rank's clock and exposed communication
@@ -229,7 +248,9 @@ def main():
     # after the timed region (it changes nothing that was measured): the collective's own bus bandwidth on this
     # node at bucket-sized messages, so the bucket cap and wire dtype can be chosen from a measurement on the
     # hardware the scaling run used (RCCL over xGMI on an 8-GPU node)
-    ar_sweep = _allreduce_sweep(dist, dev, world, bucketers) if (world > 1 and args.ar_sweep) else None
+    if args.full:
+        extra["allreduce_busbw_GBps"] = _allreduce_sweep(dist, dev, world, bucketers) if (
+            world > 1 and args.ar_sweep) else None
     ms = dt / args.steps * 1e3
     global_batch = args.batch * world
     per_sample = getattr(args, "tokens_per_sample", 1)
@@ -268,18 +289,37 @@ def main():
             # host time spent issuing a step (Python + launches); close to ms_per_step = the host, not the GPU, paces
             # the run (what hipGraph capture, bench.py --graph 1, removes)
             "host_issue_ms_per_step": round(t_issue / args.steps * 1e3, 3),
-            "host_issue_ms_single_step": round(min(single) * 1e3, 3),
             "rccl_world": rccl_world,
-            "allreduce_busbw_GBps": ar_sweep,
             "process_group_backend": backend,
-            "replicas_identical": identical,
-            "weights_checksum": csum,
         }
+        out.update(extra)  # --full only
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
     return 0
+
+
+DUMP_MAX_ELEMS = 8 << 20  # f32 elements per dumped array (32 MB)
+
+
+def _dump_outputs(path, loss, arena):
+    """--dump-outputs: what a caller of the timed step holds after the last timed step, as float32 .npy files: the
+    loss its logs carry and the f32 master weights it updated in place (every trainable variable, in arena order).
+    Weights beyond DUMP_MAX_ELEMS are sampled at fixed positions (seeded, sorted, the same for every run), so two
+    builds are compared element for element."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), np.asarray([loss], dtype=np.float32))
+    if arena is None:
+        return
+    flat = arena.flat.detach()
+    if flat.numel() > DUMP_MAX_ELEMS:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randint(0, flat.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+        flat = flat[idx.to(flat.device)]
+    np.save(os.path.join(path, "weights.npy"), flat.float().cpu().numpy())
 
 
 def _paths(bucketers):
