@@ -27,7 +27,7 @@ enum OptKind : int {
   OPT_ADADELTA = 3,  // TF1 Adadelta
   OPT_FTRL = 4,      // TF1 FTRL-proximal (lr_power = -0.5)
   OPT_RMSPROP = 5,   // TF1 RMSProp: ms = rho*ms + (1-rho) g^2; mom = m*mom + lr*g/sqrt(ms+eps); p -= mom
-  OPT_LAMB = 6,      // (per-arena trust ratio not fused; treated as AdamW here)
+  OPT_LAMB = 6,      // layer-wise rules (LAMB = 6, LARS = 7) need per-variable norms: optim_layerwise.hip
 };
 
 struct OptArgs {
@@ -209,7 +209,7 @@ DTF_API int dtf_optim_apply(int kind, float* p, float* g, float* s1, float* s2, 
   hipStream_t st = (hipStream_t)stream;
   switch (kind) {
     case OPT_SGD: launch_optim<OPT_SGD>(a, st); break;
-    case OPT_ADAM: case OPT_LAMB: launch_optim<OPT_ADAM>(a, st); break;
+    case OPT_ADAM: launch_optim<OPT_ADAM>(a, st); break;
     case OPT_ADAGRAD: launch_optim<OPT_ADAGRAD>(a, st); break;
     case OPT_ADADELTA: launch_optim<OPT_ADADELTA>(a, st); break;
     case OPT_FTRL: launch_optim<OPT_FTRL>(a, st); break;

@@ -69,6 +69,11 @@ _KERNEL_SIGS = {
     "dtf_optim_apply": [I, P, P, P, P, P, L, F, F, F, F, F, F, F, I, I, P, P, P, P],
     "dtf_sumsq": [P, L, P, I, P],
     "dtf_hp_ring_select": [P, I, I, P, P, P],
+    # layer-wise optimizers (optim_layerwise.hip): kind, [mode,] host table, device table, ntiles, nvars, sizes, ...
+    "dtf_lw_tile_elems": [],
+    "dtf_lw_pass1": [I, P, P, I, I, L, L, P, P, P, P, P, P, F, F, F, F, F, F, P, P, P, P],
+    "dtf_lw_finalize": [I, I, P, P, I, I, L, L, P, P, P, P, F, F, F, P, P],
+    "dtf_lw_pass2": [I, P, P, I, I, L, L, P, P, P, P, P, P, F, F, I, I, P, P, P, P],
     "dtf_cast_f32_bf16": [P, P, L, P],
     "dtf_cast_bf16_f32": [P, P, L, P],
     "dtf_nchw_to_nhwc_pad": [P, P, I, I, I, I, P],

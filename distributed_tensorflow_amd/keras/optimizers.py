@@ -19,21 +19,31 @@ rmsprop    decay=0.9, momentum=0, epsilon=1e-10, ms=1  ``RMSProp``, ``RMSProp_1`
 On GPU the whole variable set lives in a ``ParamArena`` and every step is ONE
 launch of ``dtf_optim_apply`` that also refreshes the bf16 compute copies.
 Per-step scalars (bias-corrected lr, gradient scale, clip threshold) go
-through a 4-float device buffer so the step stays hipGraph-capturable.
+through an ``HP_WIDTH``-float device buffer so the step stays hipGraph-capturable.
+
+The large-batch optimizers ``LARS`` and ``LAMB`` scale every variable's step by
+a ratio of per-variable L2 norms. Their step is three launches over a static
+tile table of the arena (csrc/kernels/optim_layerwise.hip: partial norms,
+one wave per variable for the ratio, the update); slots ``Momentum`` / ``m``, ``v``.
 """
 from __future__ import annotations
 
 import math
+import re
 
 import numpy as np
 import torch
 
 from ..variables import ParamArena, Variable
 from ..ops import _util
-from ..ops.optim import optim_apply, sumsq as _sumsq
+from ..ops.optim import (LW_ADAPT, LW_DECAY, LW_SCALE, LW_SUM, LayerwisePlan, layerwise_finalize, layerwise_pass1,
+                         layerwise_pass2, layerwise_tiles, optim_apply, sumsq as _sumsq)
 
 # rows of the pinned per-step scalar ring of a hipGraph-captured step (how far the host may run ahead)
 GRAPH_RING = 8
+# floats per row of per-step scalars: [lr, grad scale, clip threshold, -, 1/(1-b1^t), 1/(1-b2^t), -, -]; the
+# fused elementwise kernel reads [0..2], LAMB also [4..5]
+HP_WIDTH = 8
 
 _SLOTS = {
     "sgd": [],
@@ -44,9 +54,13 @@ _SLOTS = {
     "adadelta": [("Adadelta", 0.0), ("Adadelta_1", 0.0)],
     "ftrl": [("Ftrl", None), ("Ftrl_1", 0.0)],
     "rmsprop": [("RMSProp", None), ("RMSProp_1", 0.0)],
+    "lars": [("Momentum", 0.0)],
+    "lamb": [("m", 0.0), ("v", 0.0)],
 }
 _KERNEL_KIND = {"sgd": 0, "momentum": 0, "adam": 1, "adamw": 1, "adagrad": 2, "adadelta": 3, "ftrl": 4,
                 "rmsprop": 5}
+# layer-wise adaptive rules: per-variable norms, three launches over a tile table (ops.optim.layerwise_*)
+_LAYERWISE = ("lars", "lamb")
 
 
 class LearningRateSchedule:
@@ -108,6 +122,7 @@ class Optimizer:
         self._pinned = None
         self._host_iter = None     # host mirror of `iterations` (no device sync per step)
         self._graph = None         # set while captured in a hipGraph (see graphs.CapturedStep)
+        self._lw = {}              # layer-wise kinds: arena / shard layout -> ops.optim.LayerwisePlan
 
     # --------------------------------------------------------------- config
     def _lr_value(self, step=None):
@@ -144,6 +159,8 @@ class Optimizer:
                     v._dtf_arena = a
             for nm, init in self.slot_specs():
                 a.slot(nm, init)
+            if self.kind in _LAYERWISE:
+                self._lw_plan(a)
             self._arenas[key] = a
         return a
 
@@ -173,6 +190,8 @@ class Optimizer:
     # --------------------------------------------------------------- step math
     def _effective_lr(self, t):
         lr = self._lr_value(t - 1)
+        if self.kind in _LAYERWISE:
+            return lr  # LAMB's bias corrections cannot be folded into lr (eps): they travel as scalars of their own
         if self.kind in ("adam", "adamw"):
             b1, b2 = self.hyper.get("beta_1", 0.9), self.hyper.get("beta_2", 0.999)
             lr = lr * math.sqrt(1 - b2 ** t) / (1 - b1 ** t)
@@ -194,6 +213,12 @@ class Optimizer:
             return dict(l1=h.get("l1_regularization_strength", 0.0), l2=h.get("l2_regularization_strength", 0.0))
         if k == "rmsprop":
             return dict(b1=h.get("rho", h.get("decay", 0.9)), mom=h.get("momentum", 0.0), eps=h.get("epsilon", 1e-10))
+        if k == "lars":
+            return dict(mom=h.get("momentum", 0.9), nesterov=h.get("nesterov", False), wd=h.get("weight_decay", 0.0),
+                        eeta=h.get("eeta", 0.001), eps=h.get("epsilon", 0.0))
+        if k == "lamb":
+            return dict(b1=h.get("beta_1", 0.9), b2=h.get("beta_2", 0.999), eps=h.get("epsilon", 1e-6),
+                        wd=h.get("weight_decay", 0.0))
         raise ValueError(k)
 
     def set_grad_scale(self, s):
@@ -210,7 +235,13 @@ class Optimizer:
         self._host_iter = None
 
     def _hp_values(self, lr):
-        return [lr, self._grad_scale / self.loss_scale, float(self.global_clipnorm or 0.0), 0.0]
+        """This step's row of scalars; called before the host step counter advances."""
+        vals = [lr, self._grad_scale / self.loss_scale, float(self.global_clipnorm or 0.0)] + [0.0] * (HP_WIDTH - 3)
+        if self.kind == "lamb":
+            t = self.host_iterations() + 1
+            vals[4] = 1.0 / (1.0 - self.hyper.get("beta_1", 0.9) ** t)
+            vals[5] = 1.0 / (1.0 - self.hyper.get("beta_2", 0.999) ** t)
+        return vals
 
     def _hp_tensor(self, a, lr):
         hp = self._hp.get(id(a))
@@ -224,7 +255,7 @@ class Optimizer:
                 raise RuntimeError("optimizer arena was not prepared for graph capture (graph_prepare())")
             pinned, dev_table, ctr = ring
             dev_table.copy_(pinned, non_blocking=True)
-            _util.call("dtf_hp_ring_select", _util.ptr(dev_table), GRAPH_RING, 4, _util.ptr(ctr), _util.ptr(hp),
+            _util.call("dtf_hp_ring_select", _util.ptr(dev_table), GRAPH_RING, HP_WIDTH, _util.ptr(ctr), _util.ptr(hp),
                        _util.stream())
             return hp
         if hp is None:
@@ -234,7 +265,7 @@ class Optimizer:
         if a.device.type == "cuda":
             # ring of pinned staging buffers; a slot is reused only after its copy has executed
             if self._pinned is None:
-                self._pinned = [(torch.zeros(4, dtype=torch.float32).pin_memory(), torch.cuda.Event())
+                self._pinned = [(torch.zeros(HP_WIDTH, dtype=torch.float32).pin_memory(), torch.cuda.Event())
                                 for _ in range(8)]
                 self._ring = 0
             buf, ev = self._pinned[self._ring]
@@ -255,7 +286,9 @@ class Optimizer:
         specs = self.slot_specs()
         s1 = a.slots[specs[0][0]] if len(specs) > 0 else None
         s2 = a.slots[specs[1][0]] if len(specs) > 1 else None
-        if a.device.type == "cuda":
+        if self.kind in _LAYERWISE:
+            self._lw_apply_arena(a, t, lr, kw, s1, s2, zero_grad)
+        elif a.device.type == "cuda":
             hp = self._hp_tensor(a, lr)
             ss = None
             if self.global_clipnorm:
@@ -280,7 +313,8 @@ class Optimizer:
 
     # ---- bucket-by-bucket update during backward (collective.GradientBucketer with an optimizer attached)
     def supports_ranges(self):
-        """Elementwise update rules only: global-norm clipping needs the whole gradient first."""
+        """Elementwise update rules only: global-norm clipping needs the whole gradient first, and the layer-wise
+        rules (LARS, LAMB) whole variables' norms."""
         return not self.global_clipnorm and self.kind in _KERNEL_KIND
 
     def begin_step(self, a):
@@ -320,9 +354,9 @@ class Optimizer:
         ``segments`` = [(lo, hi, grad)] with ``grad`` the summed gradient of arena elements [lo, hi); masters,
         slots and bf16 copies are updated in place over those ranges only, one fused launch per segment.
         ``reduce_sumsq(t)`` sums a 1-element tensor over the replicas (global-norm clipping needs the norm of
-        the WHOLE gradient, of which each replica holds a part)."""
-        if self.kind == "lamb":
-            raise ValueError("LAMB's per-variable trust ratio cannot be applied to sharded optimizer state")
+        the WHOLE gradient, of which each replica holds a part). The layer-wise rules (LARS, LAMB) reduce their
+        per-variable sums of squares, a [nvars, 2] tensor, through the same hook: a variable cut by a shard
+        boundary still gets the norm of the whole variable."""
         t = self.host_iterations() + 1
         lr = self._effective_lr(t)
         kw = self._kernel_kwargs()
@@ -330,7 +364,9 @@ class Optimizer:
         s1 = a.slots[specs[0][0]] if len(specs) > 0 else None
         s2 = a.slots[specs[1][0]] if len(specs) > 1 else None
         sl = lambda s, lo, hi: None if s is None else s[lo:hi]  # noqa: E731
-        if a.device.type == "cuda":
+        if self.kind in _LAYERWISE:
+            self._lw_apply_segments(a, segments, reduce_sumsq, t, lr, kw, s1, s2)
+        elif a.device.type == "cuda":
             hp = self._hp_tensor(a, lr)
             ss = None
             if self.global_clipnorm:
@@ -364,6 +400,176 @@ class Optimizer:
             self.iterations.add_(1)
         self._host_iter = t
 
+    # ---- layer-wise adaptive rules (LARS, LAMB): keyed on self.kind / self.hyper so that a bare Optimizer rebuilt
+    # from {"kind", "hyper"} (the parameter server) runs them too
+    def _lw_flags(self, variables):
+        """Per variable: LW_DECAY unless its name matches exclude_from_weight_decay, LW_ADAPT unless it matches
+        exclude_from_layer_adaptation (None: the weight-decay list). Lists of regexes, re.search on the name."""
+        exd = list(self.hyper.get("exclude_from_weight_decay") or [])
+        exa = self.hyper.get("exclude_from_layer_adaptation")
+        exa = exd if exa is None else list(exa)
+        hit = lambda pats, v: any(re.search(p, v.name) for p in pats)  # noqa: E731
+        return [(0 if hit(exd, v) else LW_DECAY) | (0 if hit(exa, v) else LW_ADAPT) for v in variables]
+
+    @staticmethod
+    def _lw_extents(a):
+        """[lo, hi) of every variable in the arena, zero padding included."""
+        return list(zip(a.offsets, a.offsets[1:] + [a.numel]))
+
+    def _lw_plan(self, a):
+        """The whole-arena tile table and per-variable buffers (built once, at arena_for / graph_prepare time)."""
+        plan = self._lw.get(id(a))
+        if plan is None:
+            pieces = [(lo, lo, hi - lo, i) for i, (lo, hi) in enumerate(self._lw_extents(a))]
+            plan = self._lw[id(a)] = LayerwisePlan(layerwise_tiles(pieces), self._lw_flags(a.variables), a.numel,
+                                                   a.numel, a.device)
+        return plan
+
+    def _lw_clip_sumsq(self, a, grads, reduce_sumsq=None):
+        """Device sum of squares of the step's gradient pieces for global-norm clipping (None when it is off)."""
+        if not self.global_clipnorm:
+            return None
+        ss = getattr(a, "_sumsq", None)
+        if ss is None:
+            ss = a._sumsq = torch.empty(1, dtype=torch.float32, device=a.device)
+        ss.zero_()
+        for g in grads:
+            _sumsq(g, ss, zero=False)
+        if reduce_sumsq is not None:
+            reduce_sumsq(ss)
+        return ss
+
+    def _lw_host_gs(self, grads, reduce_sumsq=None):
+        """CPU arenas: the gradient scale with the global-norm clip factor folded in."""
+        gs = self._grad_scale / self.loss_scale
+        if self.global_clipnorm:
+            n2 = torch.zeros(1, dtype=torch.float64)
+            for g in grads:
+                n2 += (g.double() ** 2).sum()
+            if reduce_sumsq is not None:
+                reduce_sumsq(n2)
+            n = float(n2.sqrt()) * gs
+            if n > self.global_clipnorm:
+                gs *= self.global_clipnorm / n
+        return gs
+
+    def _lw_launch(self, plan, a, g, hp, ss, kw, s1, s2, reduce_sums=None, zero_grad=True):
+        """The three launches over ``plan``'s tiles; with ``reduce_sums`` the finalize runs in two halves around
+        the reduction of the per-variable sums over the replicas."""
+        k = self.kind
+        if k == "lamb":
+            layerwise_pass1(k, plan, a.flat, g, s1, s2, hp, b1=kw["b1"], b2=kw["b2"], eps=kw["eps"], wd=kw["wd"],
+                            sumsq=ss)
+        else:
+            layerwise_pass1(k, plan, a.flat, g, None, None, hp, sumsq=ss)
+        fin = dict(wd=kw["wd"], eeta=kw.get("eeta", 0.0), eps=kw["eps"])
+        if reduce_sums is None:
+            layerwise_finalize(k, plan, **fin)
+        else:
+            layerwise_finalize(k, plan, mode=LW_SUM, **fin)
+            reduce_sums(plan.sums)
+            layerwise_finalize(k, plan, mode=LW_SCALE, **fin)
+        # LAMB's pass 1 left its step in the gradient buffer: that one is always cleared
+        layerwise_pass2(k, plan, a.flat, g, s1 if k == "lars" else None, a.bf16, hp, wd=kw["wd"],
+                        mom=kw.get("mom", 0.0), nesterov=kw.get("nesterov", False),
+                        zero_grad=zero_grad or k == "lamb", sumsq=ss)
+        _util.bump_weights_epoch()
+
+    def _lw_torch(self, a, pieces, flags, t, lr, gs, kw, s1, s2, reduce_sums=None, zero_grad=True):
+        """Torch mirror of the three launches, variable by variable: ``pieces`` = [(lo, hi, gradient view, variable
+        index)], arena elements [lo, hi) of one variable each."""
+        k = self.kind
+        sums = torch.zeros(len(flags), 2, dtype=torch.float64)
+        with torch.no_grad():
+            for lo, hi, g, i in pieces:
+                w = a.flat[lo:hi]
+                if k == "lamb":
+                    wd = kw["wd"] if flags[i] & LW_DECAY else 0.0
+                    m, v = s1[lo:hi], s2[lo:hi]
+                    g.mul_(gs)
+                    m.mul_(kw["b1"]).add_((1 - kw["b1"]) * g)
+                    v.mul_(kw["b2"]).add_((1 - kw["b2"]) * g * g)
+                    c1, c2 = 1.0 / (1.0 - kw["b1"] ** t), 1.0 / (1.0 - kw["b2"] ** t)
+                    g.copy_((m * c1) / ((v * c2).sqrt() + kw["eps"]) + wd * w)  # u, in the gradient's place
+                    x = g
+                else:
+                    x = g * gs
+                sums[i, 0] += (w.double() ** 2).sum()
+                sums[i, 1] += (x.double() ** 2).sum()
+            if reduce_sums is not None:
+                reduce_sums(sums)
+            scale = []
+            for i, f in enumerate(flags):
+                r, (A, B) = 1.0, sums[i].tolist()
+                if f & LW_ADAPT and A > 0 and B > 0:
+                    wn, xn = math.sqrt(A), math.sqrt(B)
+                    r = wn / xn if k == "lamb" else \
+                        kw["eeta"] * wn / (xn + (kw["wd"] if f & LW_DECAY else 0.0) * wn + kw["eps"])
+                scale.append(r)
+            for lo, hi, g, i in pieces:
+                w = a.flat[lo:hi]
+                step = lr * scale[i]
+                if k == "lamb":
+                    w.sub_(step * g)
+                    g.zero_()
+                else:
+                    gg = g * gs
+                    if kw["wd"] and flags[i] & LW_DECAY:
+                        gg = gg + kw["wd"] * w
+                    acc = s1[lo:hi]
+                    acc.mul_(kw["mom"]).add_(gg)
+                    w.sub_(step * (gg + kw["mom"] * acc if kw["nesterov"] else acc))
+                    if zero_grad:
+                        g.zero_()
+
+    def _lw_apply_arena(self, a, t, lr, kw, s1, s2, zero_grad):
+        plan = self._lw_plan(a)
+        if a.device.type == "cuda":
+            hp = self._hp_tensor(a, lr)
+            ss = self._lw_clip_sumsq(a, [a.grad])
+            self._lw_launch(plan, a, a.grad, hp, ss, kw, s1, s2, zero_grad=zero_grad)
+        else:
+            gs = self._lw_host_gs([a.grad])
+            pieces = [(lo, hi, a.grad[lo:hi], i) for i, (lo, hi) in enumerate(self._lw_extents(a))]
+            self._lw_torch(a, pieces, plan.flags_host, t, lr, gs, kw, s1, s2, zero_grad=zero_grad)
+
+    def _lw_apply_segments(self, a, segments, reduce_sums, t, lr, kw, s1, s2):
+        """ZeRO-1: the owned ranges cut at the variable boundaries. Parameter offsets point into the arena,
+        gradient offsets into the compact shard buffer the segments' gradients are views of."""
+        cuda = a.device.type == "cuda"
+        key = (id(a), tuple((lo, hi, g.data_ptr()) for lo, hi, g in segments))
+        cached = self._lw.get(key)
+        if cached is None:
+            ext = self._lw_extents(a)
+            gbase = min(g.data_ptr() for _, _, g in segments)
+            gend = max(g.data_ptr() + 4 * g.numel() for _, _, g in segments)
+            cut = []  # (lo, hi, segment index, offset in the segment, variable index), in arena order
+            for k, (lo, hi, g) in enumerate(segments):
+                for i, (vlo, vhi) in enumerate(ext):
+                    plo, phi = max(lo, vlo), min(hi, vhi)
+                    if phi > plo:
+                        cut.append((plo, phi, k, plo - lo, i))
+            cut.sort()
+            plan = None
+            if cuda:
+                rows = layerwise_tiles([(plo, (segments[k][2].data_ptr() - gbase) // 4 + o, phi - plo, i)
+                                        for plo, phi, k, o, i in cut])
+                plan = LayerwisePlan(rows, self._lw_flags(a.variables), a.numel, (gend - gbase) // 4, a.device)
+            cached = self._lw[key] = (plan, cut, gbase, self._lw_flags(a.variables))
+        plan, cut, gbase, flags = cached
+        grads = [g for _, _, g in segments]
+        if cuda:
+            hp = self._hp_tensor(a, lr)
+            ss = self._lw_clip_sumsq(a, grads, reduce_sums)
+            if plan.ntiles:
+                self._lw_launch(plan, a, gbase, hp, ss, kw, s1, s2, reduce_sums=reduce_sums or (lambda s: s))
+            elif reduce_sums is not None:  # nothing owned: still take part in the replicas' reduction
+                reduce_sums(plan.sums.zero_())
+        else:
+            gs = self._lw_host_gs(grads, reduce_sums)
+            pieces = [(plo, phi, segments[k][2][o:o + phi - plo], i) for plo, phi, k, o, i in cut]
+            self._lw_torch(a, pieces, flags, t, lr, gs, kw, s1, s2, reduce_sums=reduce_sums)
+
     def graph_prepare(self):
         """Allocate (outside the capture: pinned allocation is not capturable) the fixed pinned
         scalar buffer and device hp tensor of every arena, and switch `_hp_tensor` to graph mode."""
@@ -373,11 +579,13 @@ class Optimizer:
         for a in self._arenas.values():
             if a.device.type != "cuda":
                 continue
-            self._graph[id(a)] = (torch.zeros(GRAPH_RING, 4, dtype=torch.float32).pin_memory(),
-                                  torch.zeros(GRAPH_RING, 4, dtype=torch.float32, device=a.device),
+            self._graph[id(a)] = (torch.zeros(GRAPH_RING, HP_WIDTH, dtype=torch.float32).pin_memory(),
+                                  torch.zeros(GRAPH_RING, HP_WIDTH, dtype=torch.float32, device=a.device),
                                   torch.zeros(1, dtype=torch.int32, device=a.device))
             if id(a) not in self._hp:
-                self._hp[id(a)] = torch.zeros(4, dtype=torch.float32, device=a.device)
+                self._hp[id(a)] = torch.zeros(HP_WIDTH, dtype=torch.float32, device=a.device)
+            if self.kind in _LAYERWISE:
+                self._lw_plan(a)
 
     def graph_prestep(self):
         """Before a hipGraph replay of a captured step: advance the host step and publish the step's
@@ -529,6 +737,37 @@ class RMSprop(Optimizer):
         super().__init__(learning_rate, rho=rho, momentum=momentum, epsilon=epsilon, ms_init=ms_init, **kw)
 
 
+def _regex_list(x):
+    return None if x is None else [str(p) for p in ([x] if isinstance(x, str) else x)]
+
+
+class LARS(Optimizer):
+    """Layer-wise adaptive rate scaling (TF-contrib rule) on SGD with momentum, per variable:
+    r = eeta*||w|| / (||g|| + wd*||w|| + eps) (1 when a norm is 0 or the variable is excluded from adaptation),
+    acc = momentum*acc + g + wd*w, w -= lr*r*acc. The exclusion lists are regexes searched in the variable names;
+    exclude_from_layer_adaptation=None means the weight-decay list."""
+    kind = "lars"
+
+    def __init__(self, learning_rate=0.01, momentum=0.9, weight_decay=0.0, eeta=0.001, epsilon=0.0, nesterov=False,
+                 exclude_from_weight_decay=None, exclude_from_layer_adaptation=None, **kw):
+        super().__init__(learning_rate, momentum=momentum, weight_decay=weight_decay, eeta=eeta, epsilon=epsilon,
+                         nesterov=nesterov, exclude_from_weight_decay=_regex_list(exclude_from_weight_decay),
+                         exclude_from_layer_adaptation=_regex_list(exclude_from_layer_adaptation), **kw)
+
+
+class LAMB(Optimizer):
+    """Layer-wise adaptive moments (TF-Addons rule), per variable: Adam's bias-corrected step plus decoupled weight
+    decay, u = m_hat/(sqrt(v_hat) + eps) + wd*w, scaled by the trust ratio ||w||/||u|| (1 when a norm is 0 or the
+    variable is excluded from adaptation): w -= lr*r*u. Slots ``m``, ``v``."""
+    kind = "lamb"
+
+    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-6, weight_decay=0.0,
+                 exclude_from_weight_decay=None, exclude_from_layer_adaptation=None, **kw):
+        super().__init__(learning_rate, beta_1=beta_1, beta_2=beta_2, epsilon=epsilon, weight_decay=weight_decay,
+                         exclude_from_weight_decay=_regex_list(exclude_from_weight_decay),
+                         exclude_from_layer_adaptation=_regex_list(exclude_from_layer_adaptation), **kw)
+
+
 # TF1 constructors with TF1 defaults (reference trainer/task.py:42-53)
 def GradientDescentOptimizer(learning_rate, **kw):
     return SGD(learning_rate, name="GradientDescent", **kw)
@@ -571,7 +810,7 @@ _TF1_FACTORY = {
 }
 
 _KERAS = {"sgd": SGD, "adam": Adam, "adamw": AdamW, "adagrad": Adagrad, "adadelta": Adadelta, "ftrl": Ftrl,
-          "rmsprop": RMSprop}
+          "rmsprop": RMSprop, "lars": LARS, "lamb": LAMB}
 
 
 def get(identifier, learning_rate=None, tf1=True, **kw):

@@ -316,7 +316,9 @@ class ShardedGradientBucketer(GradientBucketer):
 
     Optimizer slots keep their full-arena layout but only the owned chunks are current on each rank;
     ``gather_slots()`` (a collective: every rank must call it) all-gathers them before a checkpoint is written.
-    LAMB's per-variable trust ratio does not decompose over chunks and is rejected.
+    The layer-wise rules (LARS, LAMB) need per-variable norms while a chunk boundary may cut a variable: each rank
+    sums the squares of its own part and the [nvars, 2] sums are all-reduced before the trust ratios are formed
+    (Optimizer.apply_segments).
     SURVEY §2.6 "Reduce-scatter / all-gather (ZeRO-1, optional)".
     """
 
