@@ -155,6 +155,8 @@ enum LaunchCounter : int {
   LC_W4F8_256 = 7,    // gemm_w4_fp8.hip, 256x256 tiles
   LC_W4F8_128 = 8,    // gemm_w4_fp8.hip, 256x128 tiles
   LC_GEMM256_FP8 = 9, // gemm256.hip with fp8 operands
+  LC_ATTN_DECODE = 10,  // attn_decode.hip, split-KV single-token attention (partials + merge count as one)
+  LC_DENSE_SKINNY = 11, // attn_decode.hip, M <= 16 weight-streaming dense
   LC_COUNT = 16
 };
 DTF_API long* dtf_launch_counters();

@@ -131,6 +131,11 @@ _KERNEL_SIGS = {
     "dtf_ipc_close": [P],
     "dtf_p2p_allreduce_f32": [P, P, P, P, P, L, I, I, I, I, I, P, P],
     "dtf_memcpy_async": [P, P, L, P],
+    # KV-cached decoding (attn_decode.hip): cache append, split-KV single-token attention, M <= 16 dense
+    "dtf_kv_store": [P, P, P, P, I, I, I, I, P],
+    "dtf_attn_decode": [P, P, P, P, P, P, I, I, I, F, P],
+    "dtf_attn_decode_chunk": [],
+    "dtf_dense_skinny": [P, P, P, P, I, I, I, I, P],
 }
 
 

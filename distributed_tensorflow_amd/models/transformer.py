@@ -13,6 +13,7 @@ import math
 import torch
 
 from .. import ops
+from ..ops import decode as decode_ops
 from ..ops import mha as attn_ops
 from ..keras import layers as KL
 from ..keras.models import Model
@@ -42,7 +43,13 @@ class _Proj(KL.Layer):
         self.bias = self.add_weight("bias", (self.units,), "zeros")
         self.built = True
 
-    def call(self, x, training=None, link=None):
+    def call(self, x, training=None, link=None, cache=None):
+        if cache is not None:
+            # inference with a KV cache runs from the bf16 shadow, also for an fp8 model (sampling during training must
+            # not touch the fp8 scaling state); the one-token decode step is a weight stream (ops.dense_skinny)
+            if x.shape[-2] == 1:
+                return decode_ops.step_dense(x, self.kernel, self.bias, self.activation)
+            return ops.dense(x, self.kernel, self.bias, act=self.activation)
         if self.fp8 and x.is_cuda:
             from ..ops.fp8 import dense_fp8
             return dense_fp8(x, self.kernel, self.bias, self.activation, self, getattr(self, "_fp8_next", None))
@@ -56,10 +63,24 @@ class MultiHeadSelfAttention(KL.Layer):
         self.qkv = _Proj(3 * hidden, fp8=fp8)
         self.out = _Proj(hidden, fp8=fp8)
 
-    def call(self, x, mask=None, training=None, link=None):
+    def call(self, x, mask=None, training=None, link=None, cache=None, layer=None):
+        if cache is not None:
+            return self._call_cached(x, cache, layer)
         o = attn_ops.attention_packed(self.qkv(x, link=link), self.heads, causal=self.causal, mask=mask,
                                       dropout=self.dropout, training=training)
         return self.out(o)
+
+    def _call_cached(self, x, cache, layer):
+        """Inference with a KV cache (ops.decode.KVCache): S > 1 is the prefill of an empty cache (the causal
+        attention kernel, plus a copy of K and V into the cache), S == 1 a decode step (append, then attend)."""
+        qkv = self.qkv(x, cache=cache)
+        if x.shape[1] == 1:
+            cache.store(layer, qkv)
+            o = cache.attend(layer, qkv)
+        else:
+            o = attn_ops.attention_packed(qkv, self.heads, causal=True, dropout=0.0, training=False)
+            cache.store(layer, qkv)
+        return self.out(o, cache=cache)
 
 
 class BertLayer(KL.Layer):
@@ -152,7 +173,10 @@ class GPT2Block(KL.Layer):
         self.dropout = dropout
         object.__setattr__(self, "out_into_ln", False)  # set by GPT2: the output's first reader is a LayerNorm
 
-    def call(self, x, training=None):
+    def call(self, x, training=None, cache=None, layer=None):
+        if cache is not None:  # inference with a KV cache: no dropout, no gradient links
+            x = ops.add(x, self.att(self.ln1(x), training=False, cache=cache, layer=layer))
+            return ops.add(x, self.proj(self.fc(self.ln2(x), cache=cache), cache=cache))
         # the residual gradient of each half-block's input joins its LayerNorm's backward (ResidualGradLink)
         l1, l2 = (ResidualGradLink(), ResidualGradLink()) if (LN_LINK and training and x.is_cuda
                                                               and torch.is_grad_enabled()) else (None, None)
@@ -191,11 +215,111 @@ class GPT2(Model):
         self.dropout = dropout
         self.built = True
 
-    def call(self, ids, training=None):
+    def call(self, ids, training=None, cache=None):
+        if cache is not None:
+            return self._lm_head(self._hidden_cached(ids, cache), decode=ids.shape[1] == 1)
         x = ops.dropout(ops.embedding(ids, self.wte, self.wpe), self.dropout, training=bool(training))
         for b in self.blocks:
             x = b(x, training=training)
         return ops.dense(self.ln_f(x), self.wte, self.pad_bias)  # tied LM head, logits over vocab_p
+
+    # ---- inference with a KV cache (ops.decode)
+    def _hidden_cached(self, ids, cache):
+        """Final hidden states [B, S, hidden] of an inference forward that fills `cache`: S > 1 prefills an empty
+        cache, S == 1 is a decode step at positions cache.lens (the caller advances lens once per token)."""
+        if ids.shape[1] == 1:
+            x = ops.embedding(ids, self.wte, self.wpe, position_ids=cache.lens)
+        elif not cache.empty:
+            raise NotImplementedError("chunked prefill into a non-empty KV cache")
+        else:
+            x = ops.embedding(ids, self.wte, self.wpe)
+        for i, b in enumerate(self.blocks):
+            x = b(x, training=False, cache=cache, layer=i)
+        return self.ln_f(x)
+
+    def _lm_head(self, h, decode=False):
+        if decode:
+            return decode_ops.step_dense(h, self.wte, self.pad_bias)
+        return ops.dense(h, self.wte, self.pad_bias)
+
+    def new_cache(self, batch, capacity, device):
+        c = self.cfg
+        return decode_ops.KVCache(c["layers"], batch, c["heads"], capacity, device, head_dim=c["hidden"] // c["heads"])
+
+    def _pick(self, logits, temperature, top_k, gen):
+        """Next token per row from logits [B, vocab_p]: argmax, or temperature / top-k sampling, over the real
+        vocabulary (padded entries carry pad_bias = -1e9 and are cut off besides)."""
+        lg = logits.float()[:, :self.vocab]
+        if not temperature:
+            return lg.argmax(-1)
+        lg = lg / float(temperature)
+        if top_k is not None:
+            kth = lg.topk(min(int(top_k), self.vocab), -1).values[:, -1:]
+            lg = lg.masked_fill(lg < kth, float("-inf"))
+        return torch.multinomial(torch.softmax(lg, -1), 1, generator=gen)[:, 0]
+
+    def generate(self, ids, max_new_tokens, *, prompt_lens=None, temperature=0.0, top_k=None, seed=None,
+                 eos_token_id=None, pad_token_id=None, graph=True):
+        """Continue `ids` [B, S0] by max_new_tokens tokens with a KV cache -> int64 [B, S0 + max_new_tokens].
+
+        One prefill forward over the prompt, then one single-token step per new token (decode attention over the
+        cache, weight-streaming projections); on a GPU with graph=True the step is captured into a hipGraph and
+        replayed. prompt_lens [B]: lengths of right-padded prompts; a row's new tokens follow its prompt directly and
+        its tail is pad_token_id. temperature 0 is greedy; otherwise temperature / top-k sampling from a
+        torch.Generator seeded with `seed`. After eos_token_id a row emits pad_token_id (decided on the device: the
+        loop reads no device value and always runs max_new_tokens steps). The cache and the logits after the last
+        token are kept in ``last_generation`` (to inspect or continue)."""
+        ids = ids.long()
+        B, S0 = ids.shape
+        dev = ids.device
+        n_new = int(max_new_tokens)
+        ctx = self.cfg["ctx"]
+        if S0 + n_new > ctx:
+            raise ValueError(f"prompt ({S0}) + max_new_tokens ({n_new}) exceeds the context length {ctx}")
+        if S0 < 1 or n_new < 0:
+            raise ValueError("generate needs a non-empty prompt and max_new_tokens >= 0")
+        if n_new == 0:
+            return ids.clone()
+        pad = pad_token_id if pad_token_id is not None else (eos_token_id if eos_token_id is not None else 0)
+        gen = None
+        if temperature:
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(0 if seed is None else int(seed))
+        with torch.no_grad():
+            cache = self.new_cache(B, S0 + n_new, dev)
+            if prompt_lens is None:
+                plens = torch.full((B,), S0, dtype=torch.int64, device=dev)
+            else:
+                plens = torch.as_tensor(prompt_lens).to(dev).long()
+            h = self._hidden_cached(ids, cache)  # prefill: K/V of all S0 positions; a pad position is rewritten
+            cache.set_lens(plens)                # by the decode step that reaches it before anything attends to it
+            rows = plens - 1 + torch.arange(B, device=dev) * S0
+            last = ops.gather_rows(h.reshape(B * S0, -1), rows)  # each row's own last prompt position
+            logits = self._lm_head(last.reshape(B, 1, -1), decode=True)[:, 0]
+
+            def step(tok):
+                lg = self._lm_head(self._hidden_cached(tok, cache), decode=True)
+                cache.advance(1)
+                return lg
+
+            captured = None
+            if graph and dev.type == "cuda":
+                from ..graphs import CapturedStep
+                captured = CapturedStep(step, split=False)  # one stream only: a graph without parallel branches
+            col = torch.arange(S0, device=dev)[None, :]
+            out = torch.full((B, S0 + n_new), int(pad), dtype=torch.int64, device=dev)
+            out[:, :S0] = torch.where(col < plens[:, None], ids, out[:, :S0])
+            done = torch.zeros(B, dtype=torch.bool, device=dev)
+            for t in range(n_new):
+                tok = self._pick(logits, temperature, top_k, gen)
+                if eos_token_id is not None:
+                    tok = torch.where(done, torch.full_like(tok, int(pad)), tok)
+                    done = done | (tok == int(eos_token_id))
+                out.scatter_(1, (plens + t)[:, None], tok[:, None])
+                logits = (captured or step)(tok[:, None].contiguous())[:, 0]
+            logits = logits.clone()
+        object.__setattr__(self, "last_generation", {"cache": cache, "logits": logits, "step": captured})
+        return out
 
 
 def bert_base(**kw):

@@ -7,3 +7,4 @@ from .nn import (max_pool2d, global_avg_pool, relu, gelu, dropout, add, add_drop
                  sparse_softmax_cross_entropy, softmax, gather_rows, sort_keys)
 from .optim import optim_apply  # noqa: F401
 from .mha import attention, attention_packed  # noqa: F401
+from .decode import KVCache, dense_skinny  # noqa: F401

@@ -320,7 +320,7 @@ def gather_rows(src, idx):
 # ------------------------------------------------------------------ embeddings
 class _EmbedFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, ids, table, pos_table, type_ids, type_table, seq_len):
+    def forward(ctx, ids, table, pos_table, type_ids, type_table, seq_len, position_ids=None):
         ids = ids.contiguous().long()
         T = ids.numel()
         D = table.shape[1]
@@ -330,8 +330,8 @@ class _EmbedFn(torch.autograd.Function):
         y16 = bf16_shadow(type_table) if type_table is not None else None
         tid = type_ids.contiguous().long() if type_ids is not None else None
         out = torch.empty((T, D), dtype=BF16, device=ids.device)
-        call("dtf_embed_fwd", ptr(t16), ptr(ids), ptr(p16), None, ptr(y16), ptr(tid), ptr(out), T, D, int(seq_len),
-             stream())
+        call("dtf_embed_fwd", ptr(t16), ptr(ids), ptr(p16), ptr(position_ids), ptr(y16), ptr(tid), ptr(out), T, D,
+             int(seq_len), stream())
         ctx.save_for_backward(ids, tid)
         ctx.tables = (table, pos_table, type_table)
         ctx.shapes = (table.shape, None if pos_table is None else pos_table.shape,
@@ -374,17 +374,28 @@ class _EmbedFn(torch.autograd.Function):
         dt = None if direct[0] is not None else dt
         dp = None if direct[1] is not None else dp
         dy_ = None if direct[2] is not None else dy_
-        return None, dt, dp, None, dy_, None
+        return None, dt, dp, None, dy_, None, None
 
 
-def embedding(ids, table, pos_table=None, type_ids=None, type_table=None):
-    """out[..., :] = table[ids] (+ pos_table[position]) (+ type_table[type_ids]); positions = last axis index."""
+def embedding(ids, table, pos_table=None, type_ids=None, type_table=None, position_ids=None):
+    """out[..., :] = table[ids] (+ pos_table[position]) (+ type_table[type_ids]); positions = last axis index, or
+    position_ids (int64, one per token: the decode step passes the KV cache's lens). Explicit positions are a
+    forward-only route: the position gradient is a column sum over the batch, which assumes position = axis index."""
     seq_len = ids.shape[-1]
+    if position_ids is not None:
+        if pos_table is None:
+            raise ValueError("position_ids without a position table")
+        if pos_table.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError("embedding with position_ids has no gradient for the position table: call it under "
+                               "torch.no_grad()")
+        if position_ids.numel() != ids.numel():
+            raise ValueError("position_ids needs one position per token")
+        position_ids = position_ids.reshape(ids.shape).long().contiguous()
     if on_gpu(ids) and table.shape[1] % 8 == 0:
-        return _EmbedFn.apply(ids, table, pos_table, type_ids, type_table, seq_len)
+        return _EmbedFn.apply(ids, table, pos_table, type_ids, type_table, seq_len, position_ids)
     out = table[ids.long()]
     if pos_table is not None:
-        out = out + pos_table[:seq_len]
+        out = out + (pos_table[position_ids] if position_ids is not None else pos_table[:seq_len])
     if type_table is not None:
         out = out + (type_table[type_ids.long()] if type_ids is not None else type_table[0])
     return out

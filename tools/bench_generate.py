@@ -1,0 +1,210 @@
+"""KV-cached generation on random-init GPT-2-medium: what a decode step costs, against the recompute forward.
+
+  python tools/bench_generate.py [--out profiles/generate_decode.txt] [--rounds 5]
+
+Sections (every arm is warmed up, the arms of a comparison alternate inside each round, and the median with the
+min..max spread over the rounds is reported; times are host clocks around work that ends in a device synchronise):
+ 1. B in {1, 8}, context ~384 and ~1024: prefill, ms/token of the one-token step eager and hipGraph-captured, and the
+    recompute baseline (one full model(ids) at the same context: the only way to get the next token without a cache).
+ 2. dtf_attn_decode alone at B*H = 128, L = 1024: bytes of K and V it must read over its time, as a share of the
+    6.29 TB/s copy bandwidth. The cache rotates over 16 layers (537 MB) so the reads come from HBM, not from a cache.
+ 3. ops.dense_skinny against ops.dense on the five GPT-2-medium projection shapes at M = 1, 8, 16, rotating over
+    enough weight copies (>= 512 MB where they fit) that each call streams its weights from HBM as a decode step does.
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from distributed_tensorflow_amd import context, ops  # noqa: E402
+from distributed_tensorflow_amd.graphs import CapturedStep  # noqa: E402
+from distributed_tensorflow_amd.models.transformer import gpt2_medium  # noqa: E402
+
+COPY_BW = 6.29e12  # measured copy bandwidth of the MI355X, bytes/s
+LINES = []
+
+
+def say(s=""):
+    print(s, flush=True)
+    LINES.append(s)
+
+
+def timed(fn, iters):
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t) / iters
+
+
+def rounds_of(arms, rounds, iters):
+    """arms: {name: fn}. Warm each, then `rounds` rounds in which the arms alternate. -> {name: [seconds per call]}"""
+    for fn in arms.values():
+        timed(fn, 2)
+    res = {k: [] for k in arms}
+    for _ in range(rounds):
+        for k, fn in arms.items():
+            res[k].append(timed(fn, iters))
+    return res
+
+
+def fmt(ts, unit=1e3, u="ms"):
+    return f"{statistics.median(ts) * unit:8.3f} {u} ({min(ts) * unit:.3f}..{max(ts) * unit:.3f})"
+
+
+def graph_of(fn):
+    """fn captured into one hipGraph (after a warm-up on a side stream); returns the replay callable."""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        fn()
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        fn()
+    return g.replay
+
+
+def section_generate(dev, rounds):
+    say("== 1. GPT-2-medium (random init, bf16), KV-cached step vs recompute forward")
+    with context.device(dev), torch.no_grad():
+        model = gpt2_medium(dropout=0.0)
+        for B in (1, 8):
+            for L in (384, 1024):
+                S0, steps = L - 64, 48
+                torch.manual_seed(B * 10000 + L)
+                ids = torch.randint(0, model.vocab, (B, L), device=dev)
+                tok = ids[:, :1].contiguous()
+                cache = model.new_cache(B, L, dev)
+
+                def prefill():
+                    cache.reset()
+                    model(ids[:, :S0], training=False, cache=cache)
+                    cache.lens.fill_(S0)
+
+                def step(t):
+                    lg = model(t, training=False, cache=cache)
+                    cache.advance(1)
+                    return lg
+
+                prefill()
+                cap = CapturedStep(step, split=False)
+                for _ in range(4):
+                    cap(tok)
+                assert cap.captured
+
+                def run_steps(f):
+                    def go():
+                        cache.lens.fill_(S0)  # stay at context S0 .. S0 + steps
+                        for _ in range(steps):
+                            f(tok)
+                    return go
+
+                r = rounds_of({"eager": run_steps(step), "captured": run_steps(cap),
+                               "recompute": lambda: model(ids, training=False)}, rounds, 1)
+                pf = rounds_of({"prefill": prefill}, rounds, 1)["prefill"]
+                eager = [t / steps for t in r["eager"]]
+                capt = [t / steps for t in r["captured"]]
+                ratio = statistics.median(r["recompute"]) / statistics.median(capt)
+                say(f"B={B} context {S0}..{S0 + steps} (capacity {cache.capacity}): prefill({S0}) {fmt(pf)}")
+                say(f"    step eager    {fmt(eager)} /token")
+                say(f"    step captured {fmt(capt)} /token")
+                say(f"    recompute model(ids[{B},{L}]) {fmt(r['recompute'])} /token  -> captured step is "
+                    f"{ratio:.1f}x faster")
+                del cap, cache
+        del model
+    torch.cuda.empty_cache()
+
+
+def section_attention(dev, rounds):
+    say("== 2. dtf_attn_decode alone, B*H = 128 (B=8, H=16), L = 1024")
+    B, H, L, layers = 8, 16, 1024, 16
+    with torch.no_grad():
+        cache = ops.KVCache(layers, B, H, L, dev)
+        cache.k.normal_()
+        cache.v.normal_()
+        cache.lens.fill_(L - 1)
+        qkv = torch.randn(B, 1, 3 * H * 64, device=dev).to(torch.bfloat16)
+
+        def sweep():
+            for l in range(layers):
+                cache.attend(l, qkv)
+
+        rep = graph_of(sweep)
+        ts = [t / layers for t in rounds_of({"attn": rep}, rounds, 20)["attn"]]
+    nbytes = 2 * B * H * L * 64 * 2
+    bw = nbytes / statistics.median(ts)
+    say(f"per call (partials + merge launch, inside a replayed graph of {layers} calls over {layers} layers): "
+        f"{fmt(ts, 1e6, 'us')}; K+V bytes {nbytes / 1e6:.1f} MB -> {bw / 1e12:.2f} TB/s = "
+        f"{100 * bw / COPY_BW:.0f}% of the 6.29 TB/s copy bandwidth")
+
+
+def section_dense(dev, rounds):
+    say("== 3. ops.dense_skinny vs ops.dense, GPT-2-medium projections (K -> N), weights rotating through HBM")
+    slower = []
+    with torch.no_grad():
+        for K, N in ((1024, 3072), (1024, 1024), (1024, 4096), (4096, 1024), (1024, 50304)):
+            wbytes = N * K * 2
+            copies = max(2, min(64, (512 << 20) // wbytes))
+            ws = [torch.randn(N, K, device=dev) * 0.02 for _ in range(copies)]
+            bias = torch.zeros(N, device=dev)
+            for w in ws:
+                ops._util.bf16_shadow(w)
+            for M in (1, 8, 16):
+                x = torch.randn(M, K, device=dev).to(torch.bfloat16)
+
+                def skinny():
+                    for w in ws:
+                        ops.dense_skinny(x, w, bias)
+
+                def dense():
+                    for w in ws:
+                        ops.dense(x, w, bias)
+
+                r = rounds_of({"skinny": graph_of(skinny), "dense": graph_of(dense)}, rounds, 10)
+                sk = [t / copies for t in r["skinny"]]
+                de = [t / copies for t in r["dense"]]
+                bw = wbytes / statistics.median(sk)
+                verdict = "" if statistics.median(sk) <= statistics.median(de) else "   <-- SLOWER than ops.dense"
+                if verdict:
+                    slower.append((K, N, M))
+                say(f"{K:5d}->{N:5d} M={M:2d} ({copies:2d} copies): skinny {fmt(sk, 1e6, 'us')} "
+                    f"[{bw / 1e12:.2f} TB/s, {100 * bw / COPY_BW:.0f}% of copy bw]   dense {fmt(de, 1e6, 'us')}   "
+                    f"x{statistics.median(de) / statistics.median(sk):.2f}{verdict}")
+            del ws
+            torch.cuda.empty_cache()
+    say("shapes where dense_skinny is slower (these keep ops.dense in the decode step, ops.decode.SKINNY_EXCLUDE): "
+        + (", ".join(f"{k}->{n} at M={m}" for k, n, m in slower) if slower else "none"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                                  "profiles", "generate_decode.txt"))
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--sections", default="1,2,3")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_generate needs a GPU: nothing here can be measured on a CPU")
+    dev = torch.device("cuda", 0)
+    say(f"tools/bench_generate.py on {torch.cuda.get_device_name(0)}; rounds {a.rounds}; median (min..max)")
+    sec = set(a.sections.split(","))
+    if "2" in sec:
+        section_attention(dev, a.rounds)
+    if "3" in sec:
+        section_dense(dev, a.rounds)
+    if "1" in sec:
+        section_generate(dev, a.rounds)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("\n".join(LINES) + "\n")
+
+
+if __name__ == "__main__":
+    main()
