@@ -195,10 +195,11 @@ __global__ void __launch_bounds__(256, 1) c3_wgrad_kernel(C3Args a) {
 
 // dW [64][3][3][64] f32 (+= when accumulate) of a 64 -> 64 channel 3x3 / stride 1 / pad 1 conv over X [N][H][W][64]
 // with dY [N][H][W][64], W <= 64, on the persistent kernel. ws: >= 256 * 36864 floats. Returns 0, or -1 with nothing
-// launched when the shape is not handled.
+// launched when the shape is not handled. H >= 3: with shorter images a block that owns 4 or more rows wraps the
+// 8-slot X ring (two padding rows per image) onto rows it still needs.
 int c3_wgrad_try(const void* X, const void* dY, float* dW, int N, int H, int W, int accumulate, float* ws,
                  long ws_elems, hipStream_t st) {
-  if (((uintptr_t)X & 15) || ((uintptr_t)dY & 15) || !ws || N < 1 || H < 1 || W < 1 || W > 64) return -1;
+  if (((uintptr_t)X & 15) || ((uintptr_t)dY & 15) || !ws || N < 1 || H < 3 || W < 1 || W > 64) return -1;
   if ((long)N * (H + 2) >= (1l << 31)) return -1;
   C3Args a{};
   a.X = (const bf16_t*)X; a.dY = (const bf16_t*)dY; a.ws = ws;

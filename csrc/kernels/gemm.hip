@@ -782,6 +782,61 @@ DTF_API int dtf_set_c3_wgrad(int on) {
   g_c3_wgrad = on ? 1 : 0;
   return 0;
 }
+// DTF_W4_WGRAD3=0 (or dtf_set_w4_wgrad3(0)) keeps the spatial weight gradients into >= 256 channels on the general
+// tiles (A/B switch)
+static int g_w4_wgrad3 = -1;
+static bool w4wgrad3_enabled() {
+  if (g_w4_wgrad3 < 0) {
+    const char* e = getenv("DTF_W4_WGRAD3");
+    g_w4_wgrad3 = !(e && e[0] == '0');
+  }
+  return g_w4_wgrad3 != 0;
+}
+DTF_API int dtf_set_w4_wgrad3(int on) {
+  g_w4_wgrad3 = on ? 1 : 0;
+  return 0;
+}
+
+// Spatial (R*S > 1) weight gradient into >= 256 output channels on the 4-wave kernel with the gathered K-outer X
+// loader (gemm_w4.h W4GatherK): dW [Kout][R*S*C] = dY^T . X(gathered), split-K over the output pixels into f32 slabs
+// of ws, summed in a fixed order by dtf_sum_rows.
+// g: the weight-gradient arguments of dtf_conv_wgrad (A = dY, B = X, M = Kout, N = R*S*C, K = pixels, and the split
+// count the general tiles would use). s <= 0 keeps that split count: every output element is then the same chain of
+// MFMA accumulations over the same K ranges, summed over the same slabs by the same kernel, so dW is bit for bit what
+// the general tiles give. (A split planned for 256-row tiles, plan_w4_split_long, fills the chip better — 209-224 us
+// a layer at batch 1024 against 324-355 with this one — but reorders the f32 sums, and a training run amplifies that
+// to visibly different weights within a few steps: profiles/wgrad3x3_w4.txt.) bn <= 0: 256.
+// Returns 0 if launched, 1 if the shape is not eligible or ws too small (nothing launched).
+static int w4_wgrad3_try(const GemmArgs& g, float* dW, int accumulate, float* ws, long ws_elems, hipStream_t st,
+                         int bn, int s) {
+  if (g.M < 256) return 1;
+  GemmArgs b = g;
+  if (bn <= 0) bn = 256;
+  if (s <= 0) s = g.splitk;
+  if (bn != 128 && bn != 256) return 1;
+  const long mn = (long)b.M * b.N;
+  // ws: [slabs][pixel table, K u32]
+  const long slabs = s > 1 ? (long)s * mn : 0;
+  if (!ws || slabs + b.K > ws_elems) return 1;
+  b.pixtab = reinterpret_cast<uint32_t*>(ws + slabs);
+  if (s > 1) {
+    b.C = ws;
+    b.slab = mn;
+    b.beta = 0.f;
+  } else {
+    b.C = dW;
+    b.beta = accumulate ? 1.f : 0.f;
+  }
+  b.splitk = s;
+  b.kchunk = ((b.K + s - 1) / s + BK - 1) / BK * BK;
+  if (gemm_w4_try(b, OP_KOUTER, OP_WGRADX_R, st, bn)) return 1;
+  if (s > 1) {
+    count_launch(LC_SPLITK);
+    dtf_sum_rows(ws, mn, s, mn, dW, accumulate, st);
+  }
+  return 0;
+}
+
 // DTF_PW_WGRAD=0 (or dtf_set_pw_wgrad(0)) keeps the 1x1 weight gradients on the general tiles (A/B switch)
 static int g_pw_wgrad = -1;
 static bool pwwgrad_enabled() {
@@ -997,6 +1052,13 @@ DTF_API int dtf_conv_wgrad(const void* X, const void* dY, float* dW, int N, int 
       c3_wgrad_try(X, dY, dW, N, H, W, accumulate, ws, ws_elems, st) == 0)
     return 0;
   const bool small = (long)N * H * W * C * 2 < (1l << 31) && (long)N * P * Q * K * 2 < (1l << 31);
+  // spatial filters into >= 256 channels with >= 128 K-tiles a split (ResNet-50 stages 3-4 from batch 1024 on): the
+  // 4-wave kernel with the gathered K-outer X loader, same splits and so the same bits as the general tiles below.
+  // Measured per layer class (profiles/wgrad3x3_w4.txt): shorter splits (batch 256: ~50 K-tiles) do not repay the
+  // pixel-table kernel and the 256-row tile's prologue, and the 128-channel layers (stage 2) lose in the swapped form
+  if (tile < 0 && splitk_req <= 0 && R * S > 1 && dh == 1 && dw == 1 && small && C >= 128 && K >= 256 &&
+      a.kchunk >= 128 * BK && w4wgrad3_enabled() && w4_wgrad3_try(a, dW, accumulate, ws, ws_elems, st, 0, 0) == 0)
+    return (int)hipGetLastError();
   // spatial filters: LDS-DMA staged 128x128 (measured best for every ResNet-50 3x3 filter); 1x1 filters keep
   // the register-staged kernels (tools/conv_roofline.py --only wgrad --tiles)
   const bool use_glds = small && (tile >= 7 || (tile < 0 && R * S > 1));
@@ -1110,5 +1172,32 @@ DTF_API int dtf_conv_wgrad(const void* X, const void* dY, float* dW, int N, int 
   a.slab = mn;
   run();
   dtf_sum_rows(ws, mn, splitk, mn, dW, accumulate, st);
+  return (int)hipGetLastError();
+}
+
+// Direct entry for tests / benchmarks: the weight gradient of dtf_conv_wgrad on the 4-wave route (w4_wgrad3_try) with
+// a forced tile width bn (256 or 128; <= 0: the default) and split count (<= 0: that of the general tiles), whatever the
+// length of a split. Returns -2 if not eligible.
+DTF_API int dtf_conv_wgrad3_w4(const void* X, const void* dY, float* dW, int N, int H, int W, int C, int K, int R,
+                               int S, int P, int Q, int sh, int sw, int ph, int pw, int accumulate, int splitk,
+                               int bn, float* ws, long ws_elems, void* stream) {
+  if ((C & 7) || (K & 7) || K < 256 || (long)N * H * W * C * 2 >= (1l << 31) ||
+      (long)N * P * Q * K * 2 >= (1l << 31))
+    return -2;
+  GemmArgs a{};
+  a.g = make_geom(N, H, W, C, K, R, S, P, Q, sh, sw, ph, pw, 1, 1);
+  a.g_rowrep = rowrep(a.g.R, a.g.S);
+  a.A = (const bf16_t*)dY; a.B = (const bf16_t*)X;
+  a.M = K; a.N = R * S * C; a.K = N * P * Q;
+  a.lda = K; a.ldb = C; a.ldc = (long)R * S * C;
+  a.batch = 1;
+  a.alpha = 1.f; a.out_f32 = 1;
+  // (the split count dtf_conv_wgrad would pass on)
+  a.splitk = choose_splitk(a.M, a.N, a.K, 128, 128, 1);
+  const long mn = (long)a.M * a.N;
+  if (ws == nullptr || ws_elems < mn * 2) a.splitk = 1;
+  else if ((long)a.splitk * mn > ws_elems) a.splitk = (int)(ws_elems / mn);
+  if (a.splitk < 1) a.splitk = 1;
+  if (w4_wgrad3_try(a, dW, accumulate, ws, ws_elems, (hipStream_t)stream, bn, splitk)) return -2;
   return (int)hipGetLastError();
 }

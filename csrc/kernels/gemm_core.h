@@ -122,6 +122,9 @@ struct GemmArgs {
   // optional row sums of A over each split's K range (gemm_w4.hip, K-outer A, f32 out): rowsum[split][M] — the bias
   // gradient of a weight-gradient GEMM dW = dY^T X is the row sum of its A operand dY^T (written by the N-tile-0 blocks)
   float* rowsum;
+  // spatial weight gradient on the 4-wave kernel (gemm_w4.h W4GatherK): scratch for K = N*P*Q u32 entries, one per
+  // output pixel (its input position and which filter rows / columns fall inside the image), filled by gemm_w4_try
+  uint32_t* pixtab;
 };
 
 // 4 floats -> 4 packed OCP fp8 bytes (fmt 0 e4m3, 1 e5m2), values already scaled and clamped

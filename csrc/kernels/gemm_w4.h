@@ -163,9 +163,72 @@ struct W4Gather {
   }
 };
 
+// Pixel table of a spatial weight gradient (one u32 per output pixel k = (n, p, q), filled by w4_pixtab_kernel before
+// the GEMM): bits 0..23 the pixel index of the un-shifted input position (n, p*sh, q*sw), bit 24 + kh set when filter
+// row kh falls inside the image at this pixel, bit 27 + kw the same for filter column kw (R, S <= 3). Bits 30, 31
+// are never set.
+constexpr int W4_PT_ROW = 24, W4_PT_COL = 27;
+constexpr uint32_t W4_PT_NEVER = 0x80000000u;
+
+// Implicit-GEMM K-outer operand for the 4-wave kernels: the X side of a convolution weight gradient (OP_WGRADX_R),
+// dW[ko][tap][c] = sum over output pixels of dY[pix][ko] * X[pix shifted by tap][c]. k = output pixel (n, p, q),
+// column = (tap, input channel), C % 8 == 0 so a lane's 8-column chunk lies in one tap. Same LDS image, swizzle and
+// piece layout as W4Loader<R, OP_KOUTER> ([64 k][R cols], read by w4_frag_kouter<R>).
+// Decoding a pixel to (n, p, q) per lane, piece and K-tile (two magic-number divisions, the bounds tests and the
+// offset) compiled to ~35 VALU instructions a piece, a dozen of them 32-bit multiplies, under exec masks: more issue
+// slots than the MFMAs of a K-tile leave free with one wave per SIMD. So the decode is done once per call into the
+// pixel table above, and a piece costs one dword load of its pixel's entry, issued a K-tile ahead of its use (ent:
+// the entries of the next tile to issue), plus 4 VALU: a 24-bit multiply-add for the offset, and the bit test
+// against the lane's tap (need) that selects it or the out-of-range offset, for which the buffer range check
+// supplies zeros. The data address is all in the range-checked VGPR offset.
+template <int R>
+struct W4GatherK {
+  static constexpr int L = R / 32;
+  static constexpr int KS = 64 / L;  // k-rows between a lane's consecutive pieces
+  __amdgpu_buffer_rsrc_t rsrc, trsrc;
+  int coff[L];        // byte offset of (tap shift, channel) relative to the pixel's un-shifted input position
+  uint32_t need[L];   // the table bits of the chunk's filter row and column (a column past the operand: W4_PT_NEVER)
+  uint32_t ent[L];
+  int kr4;            // byte offset of piece 0's k-row in a tile's run of table entries
+  int C2;
+
+  __device__ __forceinline__ void init(const GemmArgs& a, const bf16_t* p, long, int r0, int Rtot, int t) {
+    const ConvGeom& g = a.g;
+    C2 = g.C * 2;
+    rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, (int)((long)g.N * g.H * g.W * g.C * 2), 0x00020000);
+    trsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.pixtab, (short)0, (int)((long)a.K * 4), 0x00020000);
+    const int kr0 = t / (R / 8);
+    kr4 = kr0 * 4;
+#pragma unroll
+    for (int i = 0; i < L; ++i) {
+      const int kr = kr0 + i * KS;
+      const int c = (t % (R / 8)) ^ (kouter_swz<R>(kr) << 1);
+      const int col = r0 + c * 8;
+      uint32_t tap, ci, kh, kw;
+      fdivmod((uint32_t)(col < Rtot ? col : 0), g.dC, tap, ci);
+      fdivmod(tap, g.dS, kh, kw);
+      need[i] = col < Rtot ? (1u << (W4_PT_ROW + kh)) | (1u << (W4_PT_COL + kw)) : W4_PT_NEVER;
+      coff[i] = (((int)kh * g.dh - g.ph) * g.W + (int)kw * g.dw - g.pw) * g.C * 2 + (int)ci * 2;
+    }
+  }
+  // the table entries of piece i of the K-tile starting at k0 (every issued tile is a real one: in range)
+  __device__ __forceinline__ void prefetch(int k0, int i) {
+    ent[i] = __builtin_amdgcn_raw_buffer_load_b32(trsrc, kr4 + i * KS * 4, k0 * 4, 0);
+  }
+  __device__ __forceinline__ void issue1(int, uint32_t lds, int i) {
+    const uint32_t e = ent[i];
+    uint32_t in = __umul24(e, (uint32_t)C2) + (uint32_t)coff[i];
+    asm volatile("" : "+v"(in));  // computed for every lane: hipcc otherwise puts it under an exec mask and a branch
+    const uint32_t off = (e & need[i]) == need[i] ? in : 0x80000000u;
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(uintptr_t)(lds + i * 4096),
+                                             16, off, 0, 0, 0);
+  }
+};
+
 template <int R, int MODE>
-using W4LoaderFor = typename std::conditional<MODE == OP_IM2COL_T || MODE == OP_DGRAD_T, W4Gather<R, MODE>,
-                                              W4Loader<R, MODE>>::type;
+using W4LoaderFor = typename std::conditional<
+    MODE == OP_IM2COL_T || MODE == OP_DGRAD_T, W4Gather<R, MODE>,
+    typename std::conditional<MODE == OP_WGRADX_R, W4GatherK<R>, W4Loader<R, MODE>>::type>::type;
 
 }  // namespace
 }  // namespace dtf

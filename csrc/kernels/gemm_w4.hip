@@ -77,7 +77,7 @@ __device__ __forceinline__ v8bf w4_frag_kouter(const char* lds, int cb, int kk, 
 }
 template <int R, int MODE>
 __device__ __forceinline__ v8bf w4_frag(const char* lds, int rb, int kk, int lane) {
-  if constexpr (MODE == OP_KOUTER) return w4_frag_kouter<R>(lds, rb, kk, lane);
+  if constexpr (MODE == OP_KOUTER || MODE == OP_WGRADX_R) return w4_frag_kouter<R>(lds, rb, kk, lane);
   else return frag_kcontig(lds, rb, kk, lane);
 }
 // Epilogue. gemm_core.h's generic gemm_epilogue serves every fused feature through runtime branches; instantiated
@@ -326,7 +326,7 @@ __global__ void __launch_bounds__(W4_THREADS, 1) gemm_w4_kernel(GemmArgs a) {
   const int nk = kend > kbeg ? (kend - kbeg + BK - 1) / BK : 0;
 
   W4LoaderFor<256, AM> la;
-  W4Loader<BN, BMODE> lb;
+  W4LoaderFor<BN, BMODE> lb;
   la.init(a, a.A + (long)bz * a.sA, a.lda, m0, a.M, threadIdx.x);
   lb.init(a, a.B + (long)bz * a.sB, a.ldb, n0, a.N, threadIdx.x);
   // LDS byte address of this wave's 1 KiB slot of piece 0 in stage 0 (wave-uniform: a scalar)
@@ -354,6 +354,10 @@ __global__ void __launch_bounds__(W4_THREADS, 1) gemm_w4_kernel(GemmArgs a) {
     const int k0 = kbeg + min(t, nk - 1) * BK;
     if (s < 8) la.issue1(k0, st, s);
     else lb.issue1(k0, st + W4_A, s - 8);
+    // a gathered weight-gradient operand: the piece's pixel-table entries of the tile after this one
+    if constexpr (BMODE == OP_WGRADX_R) {
+      if (s >= 8) lb.prefetch(kbeg + min(t + 1, nk - 1) * BK, s - 8);
+    }
   };
   auto issue = [&](int t) {
 #pragma unroll
@@ -399,7 +403,13 @@ __global__ void __launch_bounds__(W4_THREADS, 1) gemm_w4_kernel(GemmArgs a) {
     }
   };
 
-  // prologue: tiles 0 and 1 in flight, wait for tile 0 (NG LDS-DMA instructions per thread per tile)
+  // prologue: tiles 0 and 1 in flight, wait for tile 0 (NG LDS-DMA instructions per thread per tile; the pixel-table
+  // loads of a gathered weight-gradient operand only add to what vmcnt(NG) leaves outstanding after tile 0)
+  if (nk > 0) {
+#pragma unroll
+    for (int i = 0; i < BN / 32; ++i)
+      if constexpr (BMODE == OP_WGRADX_R) lb.prefetch(kbeg, i);
+  }
   if (nk > 0) issue(0);
   if (nk > 1) {
     issue(1);
@@ -476,6 +486,22 @@ __global__ void __launch_bounds__(W4_THREADS, 1) gemm_w4_kernel(GemmArgs a) {
   w4_epilogue<BN, ST>(a, acc, smem, m0, n0, z, bz);
 }
 
+// The pixel table W4GatherK reads (gemm_w4.h): one entry per output pixel of a spatial weight gradient.
+__global__ void __launch_bounds__(256) w4_pixtab_kernel(uint32_t* __restrict__ tab, int npix, ConvGeom g) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= npix) return;
+  uint32_t n, pq, p, q;
+  fdivmod((uint32_t)k, g.dPQ, n, pq);
+  fdivmod(pq, g.dQ, p, q);
+  const int hb = (int)p * g.sh, wb = (int)q * g.sw;
+  uint32_t e = (uint32_t)(((int)n * g.H + hb) * g.W + wb);
+  for (int kh = 0; kh < g.R; ++kh)
+    if ((uint32_t)(hb - g.ph + kh * g.dh) < (uint32_t)g.H) e |= 1u << (W4_PT_ROW + kh);
+  for (int kw = 0; kw < g.S; ++kw)
+    if ((uint32_t)(wb - g.pw + kw * g.dw) < (uint32_t)g.W) e |= 1u << (W4_PT_COL + kw);
+  tab[k] = e;
+}
+
 template <int AM, int BMODE, int BN, int VAR>
 void w4_go(GemmArgs& a, hipStream_t st) {
   dim3 grid(a.tiles_m * a.tiles_n, 1, a.batch * a.splitk);
@@ -502,6 +528,10 @@ void w4_launch(GemmArgs& a, int amode, int bmode, hipStream_t st) {
   if (amode == OP_DGRAD_T) {  // stride-1 data gradient, with or without the BN-backward statistics
     if (a.stats) w4_go<OP_DGRAD_T, OP_KCONTIG, BN, 16>(a, st);
     else w4_go<OP_DGRAD_T, OP_KCONTIG, BN, 0>(a, st);
+    return;
+  }
+  if (bmode == OP_WGRADX_R) {  // spatial weight gradient dW = dY^T . X(gathered)
+    w4_go<OP_KOUTER, OP_WGRADX_R, BN, 0>(a, st);
     return;
   }
 
@@ -537,6 +567,24 @@ bool gemm_w4_ok(const GemmArgs& a, int amode, int bmode) {
       return false;
     return true;
   }
+  if (amode == OP_WGRADX_R) return false;  // (the swapped form lost to the general tiles: not instantiated)
+  if (bmode == OP_WGRADX_R) {
+    // spatial weight gradient (W4GatherK), dY plain K-outer on the A side: f32 out, nothing in the epilogue but
+    // slabs or beta. K % 64 stays required: the plain operand's k position goes into the SGPR offset, which the
+    // buffer range check does not cover, so a partial last K-tile would read dY rows that do not exist.
+    const ConvGeom& g = a.g;
+    if (amode != OP_KOUTER) return false;
+    if (!a.out_f32 || a.bias || a.act || a.aux || a.dact || a.stats || a.rowsum || a.batch > 1) return false;
+    if ((g.C & 7) || (g.Kout & 7) || (a.K % BK) || (a.kchunk % BK) || (a.ldc & 3)) return false;
+    if (((uintptr_t)a.A & 15) || ((uintptr_t)a.B & 15) || ((uintptr_t)a.C & 15)) return false;
+    if ((long)g.N * g.H * g.W * g.C * 2 >= (1l << 31) || (long)a.K * g.Kout * 2 >= (1l << 31)) return false;
+    if (a.K != g.N * g.P * g.Q || a.lda != g.Kout) return false;
+    // the pixel table: 24-bit input pixel index (every un-shifted position inside the image), 3 + 3 validity bits
+    if (!a.pixtab || ((uintptr_t)a.pixtab & 3) || g.R > 3 || g.S > 3 || (long)g.N * g.H * g.W >= (1l << 24) ||
+        g.C * 2 >= (1 << 24) || (g.P - 1) * g.sh >= g.H || (g.Q - 1) * g.sw >= g.W)
+      return false;
+    return true;
+  }
   if (a.out_f32 ? (a.bias || a.act || a.aux || a.dact || (a.ldc & 3) || ((uintptr_t)a.C & 15))
                 : ((a.N & 7) || (a.ldc & 7) || ((uintptr_t)a.C & 15)))
     return false;
@@ -553,6 +601,8 @@ bool gemm_w4_ok(const GemmArgs& a, int amode, int bmode) {
 // Launch on the 4-wave kernel with tile width bn (256 or 128). Returns 0 if launched, 1 if not eligible.
 int gemm_w4_try(GemmArgs& a, int amode, int bmode, hipStream_t st, int bn) {
   if (!gemm_w4_ok(a, amode, bmode)) return 1;
+  if (bmode == OP_WGRADX_R)
+    hipLaunchKernelGGL(w4_pixtab_kernel, dim3(cdiv(a.K, 256)), dim3(256), 0, st, a.pixtab, a.K, a.g);
   count_launch(bn == 128 ? LC_W4_128 : LC_W4_256);
   if (bn == 128) w4_launch<128>(a, amode, bmode, st);
   else w4_launch<256>(a, amode, bmode, st);

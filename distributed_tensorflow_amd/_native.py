@@ -39,6 +39,8 @@ _KERNEL_SIGS = {
     "dtf_bn_bwd_coef": [P, I, P, P, P, L, I, P, P, I, P, P],
     "dtf_set_pw_wgrad": [I],
     "dtf_set_c3_wgrad": [I],
+    "dtf_set_w4_wgrad3": [I],
+    "dtf_conv_wgrad3_w4": [P, P, P] + [I] * 13 + [I, I, I, P, L, P],
     "dtf_set_split_penalty": [I],
     "dtf_set_ew_apply_nu": [I],
     "dtf_bn_bwd_partials": [P, P, P, P, P, P, L, I, P, P, P, P, I, P, I, P, P, P, P, P, P],

@@ -113,6 +113,15 @@ def main():
                     f"{t * 1e6:7.1f}us {fl / t / 1e12:6.0f}TF {byts / t / 1e12:5.2f}TB/s floor={floor * 1e6:6.1f}us "
                     f"({'mem' if byts / 5e12 > fl / 1.3e15 else 'mfma'}) x{t / floor:4.1f}")
             best = t
+            if kind == "wgrad" and R > 1 and Cin >= 128 and K >= 256:
+                # the default above is the 4-wave route (gemm_w4.hip, gathered X loader) where the splits are long
+                # enough for it; beside it the general tiles
+                call("dtf_set_w4_wgrad3", 0)
+                try:
+                    tg = timeit(mk(-1))
+                finally:
+                    call("dtf_set_w4_wgrad3", 1)
+                line += f" general:{tg * 1e6:.1f}us w4/general={t / tg:.2f}"
             if args.tiles:
                 for tile in (TILES or range(0, 11)):
                     try:
