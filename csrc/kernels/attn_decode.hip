@@ -11,6 +11,7 @@
 // the cache capacity, so a launch is identical eagerly and under hipGraph capture. No atomics: results are bitwise
 // reproducible.
 #include "common.h"
+#include "routes.h"
 
 namespace {
 

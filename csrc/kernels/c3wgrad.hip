@@ -14,10 +14,11 @@
 //  * each X row slot holds pixel x at position x + 1, positions 0 and W + 1.. stay zero (the left / right padding):
 //    tap (a, b) is the transposed read of positions k + b of tap row a — no im2col, no masks.
 // LDS layout: 128-B pixel rows with the kouter_swz<64> chunk swizzle by slot position (conflict-free for the shifted
-// reads too). Waits follow the pwwgrad.hip discipline (inline-asm LDS reads / barrier, 8 DMA pieces per thread per
-// row always, unneeded ones into a junk area with out-of-range offsets).
+// reads too). Waits follow the lds_async.h discipline (8 DMA pieces per thread per row always, unneeded ones into a
+// junk area with out-of-range offsets).
 // Reference op: the Conv2D weight gradient of the model trainer/task.py:62-71 builds.
-#include "gemm_core.h"
+#include "lds_async.h"
+#include "routes.h"
 
 namespace dtf {
 namespace {
@@ -38,26 +39,6 @@ struct C3Args {
   long rows;         // N * H output rows
   int rpb;
 };
-
-__device__ __forceinline__ v8bf c3_tr_pair(uint32_t a0, uint32_t a1) {
-  v4s r0, r1;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r0) : "v"(a0));
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r1) : "v"(a1));
-  v8s both = __builtin_shufflevector(r0, r1, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(v8bf, both);
-}
-// transposed fragment of a [pos][64] image: channels cb..cb+15, positions shift + (k-step ks's pixel slots)
-__device__ __forceinline__ v8bf c3_frag(const char* img, int cb, int shift, int ks, int lane) {
-  const int G = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-  uint32_t ad[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int pos = 32 * ks + 8 * G + 4 * h + q + shift;
-    const int g = ((cb >> 2) + p) ^ (kouter_swz<64>(pos) << 2);
-    ad[h] = (uint32_t)(uintptr_t)LDS_PTR(char, img + pos * 128 + g * 8);
-  }
-  return c3_tr_pair(ad[0], ad[1]);
-}
 
 __global__ void __launch_bounds__(256, 1) c3_wgrad_kernel(C3Args a) {
   __shared__ __attribute__((aligned(16))) char smem[C3_SMEM];
@@ -93,13 +74,10 @@ __global__ void __launch_bounds__(256, 1) c3_wgrad_kernel(C3Args a) {
 
   auto issue = [&](int it, int n, int h) {
     const long r = r0 + it;
-    const __amdgpu_buffer_rsrc_t ry =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(a.dY + r * a.W * 64), (short)0, a.W * 128, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ry = buf_rsrc(a.dY + r * a.W * 64, a.W * 128);
     char* img = dyi + (it % C3_NB) * C3_DY;
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(ry, (__attribute__((address_space(3))) void*)(img + i * 4096 + wave * 1024),
-                                               16, dok[i] ? (uint32_t)doff[i] : 0x80000000u, 0, 0, 0);
+    for (int i = 0; i < 2; ++i) dma16(ry, img + i * 4096 + wave * 1024, dok[i] ? (uint32_t)doff[i] : OOB_OFF);
     // X rows h-1 .. h+1 (virtual rows h .. h+2): all three at the block's first row and an image's first row
     const int first = (it == 0 || h == 0) ? 0 : 2;
 #pragma unroll
@@ -107,14 +85,12 @@ __global__ void __launch_bounds__(256, 1) c3_wgrad_kernel(C3Args a) {
       const int y = h - 1 + j;
       const bool need = j >= first, real = y >= 0 && y < a.H;
       const int V = n * VH + h + j;
-      const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-          (void*)(a.X + (need && real ? ((long)n * a.H + y) * a.W * 64 : 0)), (short)0, a.W * 128, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rx =
+          buf_rsrc(a.X + (need && real ? ((long)n * a.H + y) * a.W * 64 : 0), a.W * 128);
       char* dst = need ? xs + (V & (C3_NS - 1)) * C3_SLOT + 128 : junk;
 #pragma unroll
       for (int i = 0; i < 2; ++i)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            rx, (__attribute__((address_space(3))) void*)(dst + i * 4096 + wave * 1024), 16,
-            need && real && xok[i] ? (uint32_t)xoff[i] : 0x80000000u, 0, 0, 0);
+        dma16(rx, dst + i * 4096 + wave * 1024, need && real && xok[i] ? (uint32_t)xoff[i] : OOB_OFF);
     }
   };
 
@@ -140,10 +116,10 @@ __global__ void __launch_bounds__(256, 1) c3_wgrad_kernel(C3Args a) {
 
   for (int it = 0; it < n_mine; ++it) {
     // row `it` landed: after it this thread issued rows it+1, it+2 (8 pieces each, when they exist)
-    if (it + 2 < n_mine) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else if (it + 1 < n_mine) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    if (it + 2 < n_mine) vm_wait<16>();
+    else if (it + 1 < n_mine) vm_wait<8>();
+    else vm_wait<0>();
+    lds_barrier();
     if (it + C3_NB - 1 < n_mine) issue(it + C3_NB - 1, in, ih);
     next(in, ih);
     const char* img = dyi + (it % C3_NB) * C3_DY;
@@ -156,18 +132,19 @@ __global__ void __launch_bounds__(256, 1) c3_wgrad_kernel(C3Args a) {
 #pragma unroll
       for (int ta = 0; ta < 3; ++ta)
 #pragma unroll
-        for (int tb = 0; tb < 3; ++tb) x[ta * 3 + tb] = c3_frag(xr[ta], 16 * wave, tb, ks, lane);
+        for (int tb = 0; tb < 3; ++tb) x[ta * 3 + tb] = frag_kouter_async<64, true>(xr[ta], 16 * wave, ks, lane, tb);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) y[j] = c3_frag(img, 16 * j, 0, ks, lane);
+      for (int j = 0; j < 4; ++j) y[j] = frag_kouter_async<64, true>(img, 16 * j, ks, lane);
     };
     load(0, fx[0], fy[0]);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      lds_wait();
+      // (element by element: through tie()'s array form hipcc schedules this loop's scalar code differently)
 #pragma unroll
-      for (int u = 0; u < 9; ++u) asm volatile("" : "+v"(fx[ks][u]));
+      for (int u = 0; u < 9; ++u) tie(fx[ks][u]);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(fy[ks][j]));
+      for (int j = 0; j < 4; ++j) tie(fy[ks][j]);
       if (ks == 0) load(1, fx[1], fy[1]);
       // D[c][k]: src0 = X^T (rows c), src1 = dY (columns k)
 #pragma unroll

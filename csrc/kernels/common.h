@@ -16,6 +16,8 @@ typedef short v4s __attribute__((ext_vector_type(4)));
 typedef short v8s __attribute__((ext_vector_type(8)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef float v16f __attribute__((ext_vector_type(16)));
+typedef int v2i __attribute__((ext_vector_type(2)));
+typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v8i __attribute__((ext_vector_type(8)));
 
 #define LDS_PTR(T, p) ((__attribute__((address_space(3))) T*)(p))
@@ -134,30 +136,3 @@ static inline int stream_grid(long work_items, int block) {
 __global__ void __launch_bounds__(256) dtf_group_rows_kernel(float* __restrict__ rows, long stride, int nrows,
                                                              int sg, long W, float* __restrict__ out,
                                                              int accumulate);
-
-// Deterministic two-level reduction of `nrows` f32 rows (stride `stride`) into out (+= when accumulate);
-// the rows are used as scratch. Defined in gemm.hip.
-DTF_API void dtf_sum_rows(float* rows, long stride, int nrows, long W, float* out, int accumulate, void* stream);
-
-
-
-// Host-side launch counters: which GEMM kernel a call reached (read by the tests through dtf_launch_counts, so a
-// test named for a kernel fails when a dispatch change routes its call elsewhere). Incremented at launch sites on
-// the host only; no device code touches them.
-enum LaunchCounter : int {
-  LC_W4_256 = 0,      // gemm_w4.hip, 256x256 tiles
-  LC_W4_128 = 1,      // gemm_w4.hip, 256x128 tiles
-  LC_GEMM256 = 2,     // gemm256.hip (8-wave)
-  LC_GEMM_TILE = 3,   // gemm_core.h gemm_kernel (128/64-row tiles)
-  LC_GEMM_DACT = 4,   // dtf_gemm_dact (activation backward in the data-gradient epilogue)
-  LC_BETA_BF16 = 5,   // bf16 GEMM accumulating into C (beta != 0)
-  LC_SPLITK = 6,      // split-K GEMM (f32 slabs + ordered reduction)
-  LC_W4F8_256 = 7,    // gemm_w4_fp8.hip, 256x256 tiles
-  LC_W4F8_128 = 8,    // gemm_w4_fp8.hip, 256x128 tiles
-  LC_GEMM256_FP8 = 9, // gemm256.hip with fp8 operands
-  LC_ATTN_DECODE = 10,  // attn_decode.hip, split-KV single-token attention (partials + merge count as one)
-  LC_DENSE_SKINNY = 11, // attn_decode.hip, M <= 16 weight-streaming dense
-  LC_COUNT = 16
-};
-DTF_API long* dtf_launch_counters();
-inline void count_launch(int c) { dtf_launch_counters()[c]++; }

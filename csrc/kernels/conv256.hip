@@ -21,6 +21,7 @@
 // Conv2DBackpropInput / Conv2DBackpropFilter work TF's runtime does for the reference's model graph
 // (SURVEY §2.4.b K4).
 #include "gemm_core.h"
+#include "routes.h"
 
 namespace dtf {
 namespace {

@@ -3,6 +3,7 @@
 // grid-stride (Guideline 13: scalar bf16 loads cost 2-2.5x on CDNA).
 #include "common.h"
 #include "dropout_mask.h"
+#include "routes.h"
 
 namespace {
 

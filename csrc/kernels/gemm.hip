@@ -2,6 +2,7 @@
 #include <cstdlib>
 
 #include "gemm_core.h"
+#include "routes.h"
 
 // Deterministic grouped row sums (split-K slabs, BN partial rows): see common.h.
 __global__ void __launch_bounds__(256) dtf_group_rows_kernel(float* __restrict__ rows, long stride, int nrows,
@@ -262,17 +263,12 @@ static int pick_tile(long M, long N, long batch_splits, long K = 1 << 30) {
   return 3;
 }
 
-int gemm256_try(GemmArgs& a, int amode, int bmode, hipStream_t st, int fp8 = 0, int bn = 256);  // gemm256.hip
-int gemm_w4_try(GemmArgs& a, int amode, int bmode, hipStream_t st, int bn);  // gemm_w4.hip
 // 256-row tiles: the 4-wave kernel (gemm_w4.hip: 1.0-1.25x gemm256 on every transformer shape, profiles/
 // r5_gemm_vs_hipblaslt.txt) when its epilogue covers the call, else the 8-wave gemm256 kernel.
 static int tile256_try(GemmArgs& a, int amode, int bmode, hipStream_t st, int bn = 256) {
   if (gemm_w4_try(a, amode, bmode, st, bn) == 0) return 0;
   return gemm256_try(a, amode, bmode, st, 0, bn);
 }
-int conv256_try(GemmArgs& a, int amode, int bmode, int cfg, hipStream_t st, bool force);  // conv256.hip
-bool conv256_on();
-int pwconv_try(const void* X, const void* W, void* Y, float* stats, long M, int C, int K, hipStream_t st);  // pwconv.hip
 
 // The 256-row pipelined LDS-DMA kernel (conv256.hip) for a convolution GEMM: forced by tiles 11-14 (variant
 // tile - 11, see conv256.hip launch_cfg); by default whenever it is eligible and fills the chip. True if launched.
@@ -618,8 +614,6 @@ static int gemm_impl(const void* A, const void* B, void* C, void* aux, const flo
   return (int)hipGetLastError();
 }
 
-DTF_API int dtf_stem_fwd(const void* X, const void* Wt, void* Y, float* part, int* rows, int N, int Hs, int Ws, int C,
-                         int K, int R, int S, int P, int Q, void* stream);  // stem.hip
 // NHWC conv forward: Y[N,P,Q,K] = X[N,H,W,C] * W[K,R,S,C] (+bias, act, BN stats of Y)
 // stats (optional): BN partial rows [tiles_m][2K] (capacity ceil(N*P*Q/64) rows); *stat_rows = tiles_m.
 static int conv_fwd_impl(const void* X, const void* Wt, void* Y, const float* bias, float* stats, int* stat_rows,
@@ -632,10 +626,6 @@ DTF_API int dtf_conv_fwd(const void* X, const void* Wt, void* Y, const float* bi
   return conv_fwd_impl(X, Wt, Y, bias, stats, stat_rows, N, H, W, C, K, R, S, P, Q, sh, sw, ph, pw, dh, dw, act,
                        out_f32, tile, stream);
 }
-
-DTF_API int dtf_bn_finalize(float* part, int T, const float* gamma, const float* beta, float* running_mean,
-                            float* running_var, long M, int C, float momentum, float eps, float* scale,
-                            float* shift, float* mean_out, float* invstd_out, void* stream);  // norm.hip
 
 // Conv forward + training BatchNorm statistics AND their finalize: the conv launch writes per-tile partial rows of
 // sum / sum of squares, dtf_bn_finalize reduces them in a fixed order and writes scale/shift/mean/invstd and the
@@ -743,59 +733,16 @@ static int conv_dgrad_impl(const void* dY, const void* Wcrsk, void* dX, int N, i
                            const float* bnmean, float* bnpart, int* bnrows, const void* betamask,
                            const void* bsrc2, void* stream, const void* bnrx = nullptr, const void* bnrw = nullptr);
 
-namespace dtf {
-int pwconv_dgrad_try(const void* dY, const void* Wck, void* dX, float beta, const void* betamask, const void* bnx,
-                     const void* bnmask, const float* bnmean, float* part, long M, int Kc, int N, const void* bsrc2,
-                     int H, int W, hipStream_t st, const void* bnrx, const void* bnrw);
-}
-// DTF_PW_DGRAD=0 (or dtf_set_pw_dgrad(0)) keeps the pointwise data gradients on the general GEMM tiles (A/B switch)
-static int g_pw_dgrad = -1;
-static bool pwdgrad_enabled() {
-  if (g_pw_dgrad < 0) {
-    const char* e = getenv("DTF_PW_DGRAD");
-    g_pw_dgrad = !(e && e[0] == '0');
-  }
-  return g_pw_dgrad != 0;
-}
-DTF_API int dtf_set_pw_dgrad(int on) {
-  g_pw_dgrad = on ? 1 : 0;
-  return 0;
-}
-namespace dtf {
-int pw_wgrad_try(const void* X, const void* dY, float* dW, long P, int C, int K, int accumulate, float* ws,
-                 long ws_elems, hipStream_t st, bool split_out);
-}
-namespace dtf {
-int c3_wgrad_try(const void* X, const void* dY, float* dW, int N, int H, int W, int accumulate, float* ws,
-                 long ws_elems, hipStream_t st);
-}
-// DTF_C3_WGRAD=0 (or dtf_set_c3_wgrad(0)) keeps the 64-channel 3x3 weight gradients on the general tiles
-static int g_c3_wgrad = -1;
-static bool c3wgrad_enabled() {
-  if (g_c3_wgrad < 0) {
-    const char* e = getenv("DTF_C3_WGRAD");
-    g_c3_wgrad = !(e && e[0] == '0');
-  }
-  return g_c3_wgrad != 0;
-}
-DTF_API int dtf_set_c3_wgrad(int on) {
-  g_c3_wgrad = on ? 1 : 0;
-  return 0;
-}
-// DTF_W4_WGRAD3=0 (or dtf_set_w4_wgrad3(0)) keeps the spatial weight gradients into >= 256 channels on the general
-// tiles (A/B switch)
-static int g_w4_wgrad3 = -1;
-static bool w4wgrad3_enabled() {
-  if (g_w4_wgrad3 < 0) {
-    const char* e = getenv("DTF_W4_WGRAD3");
-    g_w4_wgrad3 = !(e && e[0] == '0');
-  }
-  return g_w4_wgrad3 != 0;
-}
-DTF_API int dtf_set_w4_wgrad3(int on) {
-  g_w4_wgrad3 = on ? 1 : 0;
-  return 0;
-}
+// A/B switches of the dedicated kernels: DTF_X=0 (or dtf_set_x(0)) keeps the layers on the general GEMM tiles.
+static RouteSwitch g_pw_dgrad{"DTF_PW_DGRAD", 1, false};    // pointwise data gradients (pwconv.hip MODE 3)
+static RouteSwitch g_c3_wgrad{"DTF_C3_WGRAD", 1, false};    // 64-channel 3x3 weight gradients (c3wgrad.hip)
+static RouteSwitch g_w4_wgrad3{"DTF_W4_WGRAD3", 1, false};  // spatial weight gradients into >= 256 channels (4-wave)
+// 1x1 weight gradients (pwwgrad.hip): 0 off, 1 single-tile filters, 2 also the two-tile ones
+static RouteSwitch g_pw_wgrad{"DTF_PW_WGRAD", 1, true};
+DTF_API int dtf_set_pw_dgrad(int on) { return g_pw_dgrad.set(on); }
+DTF_API int dtf_set_c3_wgrad(int on) { return g_c3_wgrad.set(on); }
+DTF_API int dtf_set_w4_wgrad3(int on) { return g_w4_wgrad3.set(on); }
+DTF_API int dtf_set_pw_wgrad(int on) { return g_pw_wgrad.set(on); }
 
 // Spatial (R*S > 1) weight gradient into >= 256 output channels on the 4-wave kernel with the gathered K-outer X
 // loader (gemm_w4.h W4GatherK): dW [Kout][R*S*C] = dY^T . X(gathered), split-K over the output pixels into f32 slabs
@@ -834,21 +781,6 @@ static int w4_wgrad3_try(const GemmArgs& g, float* dW, int accumulate, float* ws
     count_launch(LC_SPLITK);
     dtf_sum_rows(ws, mn, s, mn, dW, accumulate, st);
   }
-  return 0;
-}
-
-// DTF_PW_WGRAD=0 (or dtf_set_pw_wgrad(0)) keeps the 1x1 weight gradients on the general tiles (A/B switch)
-static int g_pw_wgrad = -1;
-static bool pwwgrad_enabled() {
-  if (g_pw_wgrad < 0) {
-    const char* e = getenv("DTF_PW_WGRAD");
-    g_pw_wgrad = e ? atoi(e) : 1;
-  }
-  return g_pw_wgrad != 0;
-}
-// 0 off, 1 single-tile filters, 2 also the two-tile ones
-DTF_API int dtf_set_pw_wgrad(int on) {
-  g_pw_wgrad = on;
   return 0;
 }
 
@@ -938,7 +870,7 @@ static int conv_dgrad_impl(const void* dY, const void* Wcrsk, void* dX, int N, i
     int t = tile;
     // channel-reducing pointwise data gradients (ResNet-50 bottleneck c1: dY width 64..256 -> 4x the channels): the
     // persistent pointwise kernel (filter in registers, beta accumulate + BN-backward partials in its store pass)
-    if (pointwise && t < 0 && !out_f32 && pwdgrad_enabled()) {
+    if (pointwise && t < 0 && !out_f32 && g_pw_dgrad.on()) {
       const int rows = pwconv_dgrad_try(dY, Wcrsk, dX, beta, betamask, bnx, bnmask, bnmean,
                                         (bnx || bnrx) ? bnpart : nullptr, a.M, K, C, bsrc2, H, W, st, bnrx, bnrw);
       if (rows > 0) {
@@ -1043,12 +975,12 @@ DTF_API int dtf_conv_wgrad(const void* X, const void* dY, float* dW, int N, int 
   a.kchunk = ((a.K + splitk - 1) / splitk + BK - 1) / BK * BK;
   bool pointwise = R == 1 && S == 1 && sh == 1 && sw == 1 && ph == 0 && pw == 0;
   // small 1x1 filters over many pixels (ResNet-50 stages 1-2): the persistent kernel, whole filter tile per block
-  if (pointwise && tile < 0 && splitk_req <= 0 && pwwgrad_enabled() &&
-      pw_wgrad_try(X, dY, dW, (long)N * H * W, C, K, accumulate, ws, ws_elems, st, g_pw_wgrad == 2) == 0)
+  if (pointwise && tile < 0 && splitk_req <= 0 && g_pw_wgrad.on() &&
+      pw_wgrad_try(X, dY, dW, (long)N * H * W, C, K, accumulate, ws, ws_elems, st, g_pw_wgrad.get() == 2) == 0)
     return 0;
   // 64 -> 64 channel 3x3 / stride 1 / pad 1 (ResNet-50 stage 1): the persistent kernel (c3wgrad.hip)
   if (tile < 0 && splitk_req <= 0 && C == 64 && K == 64 && R == 3 && S == 3 && sh == 1 && sw == 1 && ph == 1 &&
-      pw == 1 && dh == 1 && dw == 1 && P == H && Q == W && c3wgrad_enabled() &&
+      pw == 1 && dh == 1 && dw == 1 && P == H && Q == W && g_c3_wgrad.on() &&
       c3_wgrad_try(X, dY, dW, N, H, W, accumulate, ws, ws_elems, st) == 0)
     return 0;
   const bool small = (long)N * H * W * C * 2 < (1l << 31) && (long)N * P * Q * K * 2 < (1l << 31);
@@ -1057,7 +989,7 @@ DTF_API int dtf_conv_wgrad(const void* X, const void* dY, float* dW, int N, int 
   // Measured per layer class (profiles/wgrad3x3_w4.txt): shorter splits (batch 256: ~50 K-tiles) do not repay the
   // pixel-table kernel and the 256-row tile's prologue, and the 128-channel layers (stage 2) lose in the swapped form
   if (tile < 0 && splitk_req <= 0 && R * S > 1 && dh == 1 && dw == 1 && small && C >= 128 && K >= 256 &&
-      a.kchunk >= 128 * BK && w4wgrad3_enabled() && w4_wgrad3_try(a, dW, accumulate, ws, ws_elems, st, 0, 0) == 0)
+      a.kchunk >= 128 * BK && g_w4_wgrad3.on() && w4_wgrad3_try(a, dW, accumulate, ws, ws_elems, st, 0, 0) == 0)
     return (int)hipGetLastError();
   // spatial filters: LDS-DMA staged 128x128 (measured best for every ResNet-50 3x3 filter); 1x1 filters keep
   // the register-staged kernels (tools/conv_roofline.py --only wgrad --tiles)

@@ -19,6 +19,7 @@
 // Requirements (host-checked): K % 64 == 0 per split, 16-B aligned rows (lda, ldb % 8 == 0), K-outer
 // operands need their row count % 8 == 0. M, N arbitrary (edge rows clamped on load, masked on store).
 #include "gemm_core.h"
+#include "routes.h"
 
 namespace dtf {
 namespace {

@@ -3,7 +3,7 @@
 #pragma once
 #include <type_traits>
 
-#include "gemm_core.h"
+#include "lds_async.h"
 
 namespace dtf {
 namespace {
@@ -68,7 +68,7 @@ struct W4Loader {
 
   __device__ __forceinline__ void init(const GemmArgs& a, const bf16_t* p, long ld, int r0, int Rtot, int t) {
     const uint32_t bytes = MODE == OP_KCONTIG ? (uint32_t)((long)Rtot * ld * 2) : (uint32_t)((long)a.K * ld * 2);
-    rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, (int)bytes, 0x00020000);
+    rsrc = buf_rsrc(p, (int)bytes);
     kstep = MODE == OP_KCONTIG ? 2 : (int)(ld * 2);
 #pragma unroll
     for (int i = 0; i < L; ++i) {
@@ -87,8 +87,7 @@ struct W4Loader {
   }
   // piece i of the K-tile starting at k0 into the stage image at LDS byte address lds (wave-uniform)
   __device__ __forceinline__ void issue1(int k0, uint32_t lds, int i) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(uintptr_t)(lds + i * 4096),
-                                             16, (uint32_t)voff[i], k0 * kstep, 0, 0);
+    dma16(rsrc, lds + i * 4096, (uint32_t)voff[i], k0 * kstep);
   }
 };
 
@@ -115,13 +114,12 @@ struct W4Gather {
       dCh = g.dC;
       tsh = g.dh * g.W * g.C * 2;
       tsw = g.dw * g.C * 2;
-      rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, (int)((long)g.N * g.H * g.W * g.C * 2), 0x00020000);
+      rsrc = buf_rsrc(p, (int)((long)g.N * g.H * g.W * g.C * 2));
     } else {
       dCh = g.dK;
       tsh = -(g.dh * g.Q * g.Kout * 2);
       tsw = -(g.dw * g.Kout * 2);
-      rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, (int)((long)g.N * g.P * g.Q * g.Kout * 2),
-                                               0x00020000);
+      rsrc = buf_rsrc(p, (int)((long)g.N * g.P * g.Q * g.Kout * 2));
     }
 #pragma unroll
     for (int i = 0; i < L; ++i) {
@@ -157,9 +155,8 @@ struct W4Gather {
     fdivmod((uint32_t)k0, dCh, tap, c0);
     fdivmod(tap, dS, kh, kw);
     const int toff = (int)kh * tsh + (int)kw * tsw + (int)c0 * 2;
-    const uint32_t off = ((tmask[i] >> tap) & 1u) ? (uint32_t)(roff[i] + toff) : 0x80000000u;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(uintptr_t)(lds + i * 4096),
-                                             16, off, 0, 0, 0);
+    const uint32_t off = ((tmask[i] >> tap) & 1u) ? (uint32_t)(roff[i] + toff) : OOB_OFF;
+    dma16(rsrc, lds + i * 4096, off);
   }
 };
 
@@ -173,7 +170,7 @@ constexpr uint32_t W4_PT_NEVER = 0x80000000u;
 // Implicit-GEMM K-outer operand for the 4-wave kernels: the X side of a convolution weight gradient (OP_WGRADX_R),
 // dW[ko][tap][c] = sum over output pixels of dY[pix][ko] * X[pix shifted by tap][c]. k = output pixel (n, p, q),
 // column = (tap, input channel), C % 8 == 0 so a lane's 8-column chunk lies in one tap. Same LDS image, swizzle and
-// piece layout as W4Loader<R, OP_KOUTER> ([64 k][R cols], read by w4_frag_kouter<R>).
+// piece layout as W4Loader<R, OP_KOUTER> ([64 k][R cols], read by frag_kouter_async<R>).
 // Decoding a pixel to (n, p, q) per lane, piece and K-tile (two magic-number divisions, the bounds tests and the
 // offset) compiled to ~35 VALU instructions a piece, a dozen of them 32-bit multiplies, under exec masks: more issue
 // slots than the MFMAs of a K-tile leave free with one wave per SIMD. So the decode is done once per call into the
@@ -195,8 +192,8 @@ struct W4GatherK {
   __device__ __forceinline__ void init(const GemmArgs& a, const bf16_t* p, long, int r0, int Rtot, int t) {
     const ConvGeom& g = a.g;
     C2 = g.C * 2;
-    rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, (int)((long)g.N * g.H * g.W * g.C * 2), 0x00020000);
-    trsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.pixtab, (short)0, (int)((long)a.K * 4), 0x00020000);
+    rsrc = buf_rsrc(p, (int)((long)g.N * g.H * g.W * g.C * 2));
+    trsrc = buf_rsrc(a.pixtab, (int)((long)a.K * 4));
     const int kr0 = t / (R / 8);
     kr4 = kr0 * 4;
 #pragma unroll
@@ -219,9 +216,8 @@ struct W4GatherK {
     const uint32_t e = ent[i];
     uint32_t in = __umul24(e, (uint32_t)C2) + (uint32_t)coff[i];
     asm volatile("" : "+v"(in));  // computed for every lane: hipcc otherwise puts it under an exec mask and a branch
-    const uint32_t off = (e & need[i]) == need[i] ? in : 0x80000000u;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(uintptr_t)(lds + i * 4096),
-                                             16, off, 0, 0, 0);
+    const uint32_t off = (e & need[i]) == need[i] ? in : OOB_OFF;
+    dma16(rsrc, lds + i * 4096, off);
   }
 };
 

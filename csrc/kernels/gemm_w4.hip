@@ -21,13 +21,12 @@
 //   * Per-lane DMA state is loop-invariant (the tile's k goes into the SGPR offset, the LDS destination is M0), so a
 //     piece is s_add + s_mov m0 + buffer_load.
 //   * MFMAs are inline asm with a tied AGPR accumulator (w4_mfma), K-outer fragments inline-asm transposed reads
-//     (w4_frag_kouter): see those for why.
+//     (lds_async.h frag_kouter_async): see those for why.
 // Epilogue: w4_epilogue (LDS-staged 16-B row stores for bf16 outputs).
 // Reference op family: MatMul and its gradients in the TF graph the reference builds (SURVEY §2.4.b K3;
 // /root/reference/trainer/task.py:137-139).
-#include <cstdlib>
-
 #include "gemm_w4.h"
+#include "routes.h"
 
 namespace dtf {
 namespace {
@@ -57,27 +56,9 @@ struct W4Geo {
 __device__ __forceinline__ void w4_mfma(v4f& c, const v8bf& b, const v8bf& a) {
   asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(b), "v"(a));
 }
-// Transposed fragment of a K-outer [64 k][R cols] image (frag_kouter<R>'s addressing) read by inline-asm
-// ds_read_b64_tr_b16: the builtin makes hipcc wait vmcnt for the in-flight LDS-DMA of the OTHER stage before every
-// such read (it cannot tell the two apart), which drained the prefetch every K-tile (NN / TN 0.4-0.5x of NT). hipcc
-// neither sees nor waits for these asm reads: the main loop waits lgkmcnt(0) before the MFMAs that consume them.
-template <int R>
-__device__ __forceinline__ v8bf w4_frag_kouter(const char* lds, int cb, int kk, int lane) {
-  const int G = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-  v4s r[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int k = 32 * kk + 8 * G + 4 * h + q;
-    const int g = ((cb >> 2) + p) ^ (kouter_swz<R>(k) << 2);
-    const uint32_t addr = (uint32_t)(uintptr_t)LDS_PTR(char, lds + k * (R * 2) + g * 8);
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r[h]) : "v"(addr));
-  }
-  v8s both = __builtin_shufflevector(r[0], r[1], 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(v8bf, both);
-}
 template <int R, int MODE>
 __device__ __forceinline__ v8bf w4_frag(const char* lds, int rb, int kk, int lane) {
-  if constexpr (MODE == OP_KOUTER || MODE == OP_WGRADX_R) return w4_frag_kouter<R>(lds, rb, kk, lane);
+  if constexpr (MODE == OP_KOUTER || MODE == OP_WGRADX_R) return frag_kouter_async<R>(lds, rb, kk, lane);
   else return frag_kcontig(lds, rb, kk, lane);
 }
 // Epilogue. gemm_core.h's generic gemm_epilogue serves every fused feature through runtime branches; instantiated
@@ -413,10 +394,10 @@ __global__ void __launch_bounds__(W4_THREADS, 1) gemm_w4_kernel(GemmArgs a) {
   if (nk > 0) issue(0);
   if (nk > 1) {
     issue(1);
-    if constexpr (NG == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+    if constexpr (NG == 16) vm_wait<16>();
+    else vm_wait<12>();
   } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<0>();
   }
   w4_barrier();
   if (nk > 0) {
@@ -472,7 +453,7 @@ __global__ void __launch_bounds__(W4_THREADS, 1) gemm_w4_kernel(GemmArgs a) {
       }
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  vm_wait<0>();
   __syncthreads();  // the epilogue reuses the LDS
   if constexpr ((VAR & 4) != 0) {  // ablation: no epilogue (one store of a value that depends on every accumulator)
     float x = 0.f;

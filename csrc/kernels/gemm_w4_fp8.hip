@@ -21,6 +21,7 @@
 //                                                              [n0 + BN/2 wn + 32 j + 8 q + 4 (l >> 5) + p].
 // Reference op family: the GPT-2-medium fp8 projections of BASELINE.json ("CDNA4 fp8 MFMA"); SURVEY §2.4.b K3f.
 #include "gemm_w4.h"
+#include "routes.h"
 
 namespace dtf {
 namespace {
@@ -40,12 +41,11 @@ struct W8Geo {
 // Inline-asm ds_read_b128: with two LDS-DMA pieces per step in flight hipcc cannot tell them from these reads and
 // put vmcnt(0) ahead of every read (the prefetch drained 4x per K-tile); the main loop waits lgkmcnt(0) itself
 // before the MFMAs that consume a fragment set.
-typedef int v4i_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ v8i w8_frag(const char* lds, int rb, int kk, int lane) {
   const int row = rb + (lane & 31), G = lane >> 5, sw = (row >> 1) & 7;
   const int c0 = 4 * kk + 2 * G;
-  const uint32_t base = (uint32_t)(uintptr_t)LDS_PTR(char, lds + row * 128);
-  v4i_t lo, hi;
+  const uint32_t base = lds_addr(lds + row * 128);
+  v4i lo, hi;
   asm volatile("ds_read_b128 %0, %1" : "=v"(lo) : "v"(base + ((c0 ^ sw) << 4)));
   asm volatile("ds_read_b128 %0, %1" : "=v"(hi) : "v"(base + (((c0 + 1) ^ sw) << 4)));
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
@@ -337,10 +337,10 @@ __global__ void __launch_bounds__(W4_THREADS, 1) gemm_w4_fp8_kernel(GemmArgs a) 
   if (nk > 0) issue(0);
   if (nk > 1) {
     issue(1);
-    if constexpr (NG == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+    if constexpr (NG == 16) vm_wait<16>();
+    else vm_wait<12>();
   } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<0>();
   }
   w4_barrier();
   if (nk > 0) read(fa0, fb0, 0, 0);
@@ -377,7 +377,7 @@ __global__ void __launch_bounds__(W4_THREADS, 1) gemm_w4_fp8_kernel(GemmArgs a) 
     for (int s = 0; s < NSTEP; ++s) mma2(fa1, fb1, s);
   }
   w8_mfma_drain();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  vm_wait<0>();
   __syncthreads();
   w8_epilogue<BN>(a, acc, smem, m0, n0, z);
 }

@@ -12,6 +12,7 @@
 //   write one partial row per block (no same-address atomics: deterministic).
 #include "common.h"
 #include "dropout_mask.h"
+#include "routes.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -955,10 +956,6 @@ DTF_API int dtf_bn_stats(const void* x, long M, int C, float* part, int* rows, v
   *rows = G;
   return (int)hipGetLastError();
 }
-
-DTF_API void dtf_sum_rows(float* rows, long stride, int nrows, long W, float* out, int accumulate, void* stream);
-DTF_API int dtf_group_rows_once(float* rows, long stride, int nrows, long W, int target, long* out_stride,
-                                void* stream);
 
 DTF_API int dtf_bn_finalize(float* part, int T, const float* gamma, const float* beta, float* running_mean,
                             float* running_var, long M, int C, float momentum, float eps, float* scale,

@@ -5,20 +5,19 @@
 // The separate kernels read dY — the 4x-wide tensor, 4 of the 5 activation widths either of them reads — twice (the
 // dgrad on the main stream, the wgrad on the side stream: 1.64 GB each per layer at batch 1024). Here each 64-pixel
 // dY tile arrives once by LDS-DMA as a K-outer image that serves both products: the weight gradient reads it
-// transposed (ds_read_b64_tr_b16, frag_kouter's addressing), the data gradient row-wise (16-B reads at the same
-// swizzled chunks) against the filter held in registers. X (the layer input, 64 channels) rides in the same ring.
+// transposed (frag_kouter_async), the data gradient row-wise (row_frag: 16-B reads at the same swizzled chunks)
+// against the filter held in registers. X (the layer input, 64 channels) rides in the same ring (lds_async.h).
 // The dX tile is staged through LDS and stored as 16-B row chunks with the BN partials of the stored values.
 // pw_bwd_bn_kernel (below) goes further: dY itself is never stored — it is the BatchNorm(+ReLU) backward of the conv
 // output y, computed per tile from dout, y and the ReLU bits (stage 1 and stage 2 shapes); optionally y is not stored
 // either and is recomputed from the X tile (YR), and the same pass takes a projection shortcut's BN-backward sums (SC).
 // Measured effects: profiles/r6_fused_1x1_backward.txt.
 // Reference op: the Conv2D gradients of the model trainer/task.py:62-71 builds.
-#include "gemm_core.h"
+#include "lds_async.h"
+#include "routes.h"
 
 namespace dtf {
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 struct PbArgs {
   const bf16_t* dY;   // [P][K]
@@ -31,60 +30,6 @@ struct PbArgs {
   float* part;        // [slots][2C]
   float* ws;          // [slots][K][C] weight-gradient partials
   int P, tiles_p, slots;
-};
-
-template <int R>
-__device__ __forceinline__ v8bf tr_frag(const char* lds, int cb, int kk, int lane) {
-  const int G = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-  v4s r[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int k = 32 * kk + 8 * G + 4 * h + q;
-    const int g = ((cb >> 2) + p) ^ (kouter_swz<R>(k) << 2);
-    const uint32_t addr = (uint32_t)(uintptr_t)LDS_PTR(char, lds + k * (R * 2) + g * 8);
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r[h]) : "v"(addr));
-  }
-  v8s both = __builtin_shufflevector(r[0], r[1], 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(v8bf, both);
-}
-
-// row fragment of the same K-outer image: pixel row pr + (lane & 15), channels 32 s + 8 (lane >> 4) .. +7
-template <int R>
-__device__ __forceinline__ v8bf row_frag(const char* lds, int pr, int s, int lane) {
-  const int row = pr + (lane & 15);
-  const int c16 = 4 * s + (lane >> 4);
-  const int pc = c16 ^ (kouter_swz<R>(row) << 1);
-  const uint32_t addr = (uint32_t)(uintptr_t)LDS_PTR(char, lds + row * (R * 2) + pc * 16);
-  v4i r;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(addr));
-  return __builtin_bit_cast(v8bf, r);
-}
-
-template <int R>
-struct KoDma {  // LDS-DMA of a [64 pixel][R] slice into the K-outer image (pwwgrad.hip WgOperand)
-  static constexpr int L = R / 32;
-  __amdgpu_buffer_rsrc_t rsrc;
-  int kr[L], coff[L];
-  __device__ __forceinline__ void init(const bf16_t* p, long rows) {
-    const int t = threadIdx.x;
-    rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, (int)(rows * R * 2), 0x00020000);
-#pragma unroll
-    for (int i = 0; i < L; ++i) {
-      const int pb = i * 4096 + t * 16;
-      kr[i] = pb / (R * 2);
-      coff[i] = ((((pb % (R * 2)) >> 4) ^ (kouter_swz<R>(kr[i]) << 1)) * 16);
-    }
-  }
-  __device__ __forceinline__ void issue(int p0, int P, char* lds) {
-    const int wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < L; ++i) {
-      const int p = p0 + kr[i];
-      const uint32_t off = p < P ? (uint32_t)(p * (R * 2) + coff[i]) : 0x80000000u;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          rsrc, (__attribute__((address_space(3))) void*)(lds + i * 4096 + wave * 1024), 16, off, 0, 0, 0);
-    }
-  }
 };
 
 template <int K, int C>
@@ -110,10 +55,10 @@ __global__ void __launch_bounds__(256, 1) pw_bwd_kernel(PbArgs a) {
 #pragma unroll
   for (int s = 0; s < K / 32; ++s) asm volatile("" ::"v"(fw[s]));
 
-  KoDma<K> dmy;
-  KoDma<C> dmx;
-  dmy.init(a.dY, a.P);
-  dmx.init(a.X, a.P);
+  KOuterDma<K> dmy;
+  KOuterDma<C> dmx;
+  dmy.init(a.dY, a.P, K, 0);
+  dmx.init(a.X, a.P, C, 0);
   auto issue = [&](int tile, int buf) {
     char* img = smem + buf * IMG;
     dmy.issue(tile * 64, a.P, img);
@@ -126,12 +71,9 @@ __global__ void __launch_bounds__(256, 1) pw_bwd_kernel(PbArgs a) {
 
   // BN partials of dX: this thread's 8-channel chunk is fixed (256 % CH == 0)
   const int ch = t % CH, nch = ch * 8;
-  const __amdgpu_buffer_rsrc_t dxr =
-      __builtin_amdgcn_make_buffer_rsrc((void*)a.dX, (short)0, (int)((long)a.P * C * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t xbr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)a.bnx, (short)0, a.bnmean ? (int)((long)a.P * C * 2) : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t xmr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)a.bnmask, (short)0, a.bnmask ? (int)((long)a.P * C / 8) : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t dxr = buf_rsrc(a.dX, (int)((long)a.P * C * 2));
+  const __amdgpu_buffer_rsrc_t xbr = buf_rsrc(a.bnx, a.bnmean ? (int)((long)a.P * C * 2) : 0);
+  const __amdgpu_buffer_rsrc_t xmr = buf_rsrc(a.bnmask, a.bnmask ? (int)((long)a.P * C / 8) : 0);
   const uint32_t xm_or = a.bnmask ? 0u : 0xFFu;
   float mu[8], bs[8], bq[8];
 #pragma unroll
@@ -150,12 +92,12 @@ __global__ void __launch_bounds__(256, 1) pw_bwd_kernel(PbArgs a) {
     // tile `it` landed. Issued after it: tile it+1's DMA (a dummy one past the last tile; none when n_mine == 1 at
     // it 0) and, from iteration 1 on, tile it-1's ST stores
     if (it == 0) {
-      if (n_mine > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LD) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (n_mine > 1) vm_wait<LD>();
+      else vm_wait<0>();
     } else {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LD + ST) : "memory");
+      vm_wait<LD + ST>();
     }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    lds_barrier();
     const int tile = slot + it * step;
     // this tile's BN inputs and mask bytes, in flight under the MFMAs (issued before tile it+2's DMA)
     uint4 xv[ST];
@@ -165,8 +107,8 @@ __global__ void __launch_bounds__(256, 1) pw_bwd_kernel(PbArgs a) {
       const int p = tile * 64 + ((t + 256 * k) / CH);
       const uint32_t e = (uint32_t)p * C + nch;
       const bool ok = p < a.P;
-      xv[k] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(xbr, ok ? e * 2u : 0x80000000u, 0, 0));
-      xmb[k] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(xmr, ok ? e >> 3 : 0x80000000u, 0, 0);
+      xv[k] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(xbr, ok ? e * 2u : OOB_OFF, 0, 0));
+      xmb[k] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(xmr, ok ? e >> 3 : OOB_OFF, 0, 0);
     }
     // (issued unconditionally — past the last tile every row is out of range and the ring buffer no tile uses gets
     // zeros — so the compiler's wait counts for the loads above stay the same on every iteration)
@@ -178,14 +120,12 @@ __global__ void __launch_bounds__(256, 1) pw_bwd_kernel(PbArgs a) {
     for (int kk = 0; kk < 2; ++kk) {
       v8bf fx[4], fy[4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) fx[i] = tr_frag<C>(img + IMG_Y, 16 * i, kk, lane);
+      for (int i = 0; i < 4; ++i) fx[i] = frag_kouter_async<C>(img + IMG_Y, 16 * i, kk, lane);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) fy[j] = tr_frag<K>(img, 64 * wave + 16 * j, kk, lane);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(fx[i]));
-#pragma unroll
-      for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(fy[j]));
+      for (int j = 0; j < 4; ++j) fy[j] = frag_kouter_async<K>(img, 64 * wave + 16 * j, kk, lane);
+      lds_wait();
+      tie(fx);
+      tie(fy);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -201,37 +141,29 @@ __global__ void __launch_bounds__(256, 1) pw_bwd_kernel(PbArgs a) {
       v8bf fa[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) fa[i] = row_frag<K>(img, 16 * i, s, lane);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(fa[i]));
+      lds_wait();
+      tie(fa);
 #pragma unroll
       for (int i = 0; i < 4; ++i) ad[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[s], fa[i], ad[i], 0, 0, 0);
     }
-    // stage the bf16 dX tile (inline-asm LDS stores: see pwconv.hip stage_write)
+    // stage the bf16 dX tile
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int pl = 16 * i + (lane & 15), cl = 16 * wave + 4 * (lane >> 4);
       uint2 o;
       o.x = pack2bf(ad[i][0], ad[i][1]);
       o.y = pack2bf(ad[i][2], ad[i][3]);
-      const uint32_t addr = (uint32_t)(uintptr_t)LDS_PTR(char, stg + (pl * SROW + cl) * 2);
-      asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(o) : "memory");
+      lds_store8(stg + (pl * SROW + cl) * 2, o);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // the tile is staged
+    lds_barrier();  // the tile is staged
     // the BN loads are in: everything but tile it+2's DMA (issued after them) has completed
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LD) : "memory");
+    vm_wait<LD>();
 #pragma unroll
     for (int k = 0; k < ST; ++k) {
       const int pl = (t + 256 * k) / CH;
       const int p = tile * 64 + pl;
-      uint4 val;
-      {
-        const uint32_t addr = (uint32_t)(uintptr_t)LDS_PTR(char, stg + (pl * SROW + nch) * 2);
-        v4i r;
-        asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(r) : "v"(addr) : "memory");
-        val = __builtin_bit_cast(uint4, r);
-      }
-      const uint32_t off = p < a.P ? ((uint32_t)p * C + nch) * 2u : 0x80000000u;
+      const uint4 val = lds_load16(stg + (pl * SROW + nch) * 2);
+      const uint32_t off = p < a.P ? ((uint32_t)p * C + nch) * 2u : OOB_OFF;
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, val), dxr, off, 0, 0);
       const uint32_t vw[4] = {val.x, val.y, val.z, val.w}, xw[4] = {xv[k].x, xv[k].y, xv[k].z, xv[k].w};
 #pragma unroll
@@ -260,7 +192,7 @@ __global__ void __launch_bounds__(256, 1) pw_bwd_kernel(PbArgs a) {
     }
   if (!a.bnmean) return;
   // ---- one BN partial row per block: the 256 / CH threads of each chunk folded through LDS in a fixed order
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the dummy DMA past the last tile has landed too
+  vm_wait<0>();  // the dummy DMA past the last tile has landed too
   __syncthreads();  // every tile's reads of the ring are done
   float* red = reinterpret_cast<float*>(smem);
 #pragma unroll
@@ -367,17 +299,13 @@ __global__ void __launch_bounds__(256, 1) pw_bwd_bn_kernel(PbnArgs A) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) asm volatile("" ::"v"(ka[j]), "v"(kb[j]), "v"(kc[j]));
 
-  const __amdgpu_buffer_rsrc_t dr =
-      __builtin_amdgcn_make_buffer_rsrc((void*)A.dout, (short)0, (int)((long)a.P * K * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t yr =
-      __builtin_amdgcn_make_buffer_rsrc((void*)A.y, (short)0, (int)((long)a.P * K * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t mr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)A.ymask, (short)0, A.ymask ? (int)((long)a.P * K / 8) : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t dr = buf_rsrc(A.dout, (int)((long)a.P * K * 2));
+  const __amdgpu_buffer_rsrc_t yr = buf_rsrc(A.y, (int)((long)a.P * K * 2));
+  const __amdgpu_buffer_rsrc_t mr = buf_rsrc(A.ymask, A.ymask ? (int)((long)a.P * K / 8) : 0);
   const uint32_t ym_or = A.ymask ? 0u : 0xFFu;
   uint4 dv[U], yv[U], sv_[SC ? U : 1];
   uint32_t mb[U];
-  const __amdgpu_buffer_rsrc_t scr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)A.ysc, (short)0, SC ? (int)((long)a.P * K * 2) : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t scr = buf_rsrc(A.ysc, SC ? (int)((long)a.P * K * 2) : 0);
   float ssc[8], qsc[8], msc[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
@@ -390,28 +318,20 @@ __global__ void __launch_bounds__(256, 1) pw_bwd_bn_kernel(PbnArgs A) {
       const int p = tile * BMP + ry + RPT * u;
       const uint32_t e = (uint32_t)p * K + cy * 8;
       const bool ok = p < a.P;
-      dv[u] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(dr, ok ? e * 2u : 0x80000000u, 0, 0));
+      dv[u] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(dr, ok ? e * 2u : OOB_OFF, 0, 0));
       if constexpr (!YR)
-        yv[u] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(yr, ok ? e * 2u : 0x80000000u, 0, 0));
-      mb[u] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(mr, ok ? e >> 3 : 0x80000000u, 0, 0);
+        yv[u] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(yr, ok ? e * 2u : OOB_OFF, 0, 0));
+      mb[u] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(mr, ok ? e >> 3 : OOB_OFF, 0, 0);
       if constexpr (SC)
-        sv_[u] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(scr, ok ? e * 2u : 0x80000000u, 0, 0));
+        sv_[u] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(scr, ok ? e * 2u : OOB_OFF, 0, 0));
     }
   };
   auto transform = [&](int tile, char* img) {  // dY = a dz + b y + c -> bf16 -> the K-outer image
     if constexpr (YR) {  // this tile's y chunks from the LDS stage
-      v4i yr4[U];
+      int yo[U];
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const uint32_t addr = (uint32_t)(uintptr_t)LDS_PTR(char, ystg + ((ry + RPT * u) * YROW + cy * 8) * 2);
-        asm volatile("ds_read_b128 %0, %1" : "=v"(yr4[u]) : "v"(addr));
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        asm volatile("" : "+v"(yr4[u]));
-        yv[u] = __builtin_bit_cast(uint4, yr4[u]);
-      }
+      for (int u = 0; u < U; ++u) yo[u] = ((ry + RPT * u) * YROW + cy * 8) * 2;
+      lds_load16(yv, ystg, yo);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -438,14 +358,13 @@ __global__ void __launch_bounds__(256, 1) pw_bwd_bn_kernel(PbnArgs A) {
       const v4i w4 = {(int)pack2bf(o[0], o[1]), (int)pack2bf(o[2], o[3]), (int)pack2bf(o[4], o[5]),
                       (int)pack2bf(o[6], o[7])};
       const int pc = cy ^ (kouter_swz<K>(row) << 1);
-      const uint32_t addr = (uint32_t)(uintptr_t)LDS_PTR(char, img + row * (K * 2) + pc * 16);
-      asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(w4) : "memory");
+      lds_store16(img + row * (K * 2) + pc * 16, w4);
     }
   };
 
-  // X: the [BMP][CB] column block of rows with stride C, by LDS-DMA into a K-outer image (pwwgrad.hip's mapping)
-  const __amdgpu_buffer_rsrc_t xsr =
-      __builtin_amdgcn_make_buffer_rsrc((void*)a.X, (short)0, (int)((long)a.P * C * 2), 0x00020000);
+  // X: the [BMP][CB] column block of rows with stride C, KOuterDma<CB>'s mapping for BMP rows (kept inline: through the struct
+  // hipcc allocates this kernel's registers differently)
+  const __amdgpu_buffer_rsrc_t xsr = buf_rsrc(a.X, (int)((long)a.P * C * 2));
   int xkr[LDX], xco[LDX];
 #pragma unroll
   for (int i = 0; i < LDX; ++i) {
@@ -457,9 +376,8 @@ __global__ void __launch_bounds__(256, 1) pw_bwd_bn_kernel(PbnArgs A) {
 #pragma unroll
     for (int i = 0; i < LDX; ++i) {
       const int p = tile * BMP + xkr[i];
-      const uint32_t off = p < a.P ? (uint32_t)(p * (C * 2) + xco[i]) : 0x80000000u;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          xsr, (__attribute__((address_space(3))) void*)(img + i * 4096 + wave * 1024), 16, off, 0, 0, 0);
+      const uint32_t off = p < a.P ? (uint32_t)(p * (C * 2) + xco[i]) : OOB_OFF;
+      dma16(xsr, img + i * 4096 + wave * 1024, off);
     }
   };
 
@@ -472,12 +390,9 @@ __global__ void __launch_bounds__(256, 1) pw_bwd_bn_kernel(PbnArgs A) {
   x_issue(tile_of(1), ximg + IMG_X);
 
   const int ch = t % CH, nch = c0 + ch * 8;
-  const __amdgpu_buffer_rsrc_t dxr =
-      __builtin_amdgcn_make_buffer_rsrc((void*)a.dX, (short)0, (int)((long)a.P * C * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t xbr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)a.bnx, (short)0, a.bnmean ? (int)((long)a.P * C * 2) : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t xmr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)a.bnmask, (short)0, a.bnmask ? (int)((long)a.P * C / 8) : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t dxr = buf_rsrc(a.dX, (int)((long)a.P * C * 2));
+  const __amdgpu_buffer_rsrc_t xbr = buf_rsrc(a.bnx, a.bnmean ? (int)((long)a.P * C * 2) : 0);
+  const __amdgpu_buffer_rsrc_t xmr = buf_rsrc(a.bnmask, a.bnmask ? (int)((long)a.P * C / 8) : 0);
   const uint32_t xm_or = a.bnmask ? 0u : 0xFFu;
   float mu[8], bs[8], bq[8];
 #pragma unroll
@@ -494,14 +409,14 @@ __global__ void __launch_bounds__(256, 1) pw_bwd_bn_kernel(PbnArgs A) {
   for (int it = 0; it < n_mine; ++it) {
     // this tile's registers and X image are in. Issued after them: X of tile it+1 (LDX) and, from iteration 1 on,
     // the ST dX stores of tile it-1
-    if (it == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LDX) : "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LDX + ST) : "memory");
+    if (it == 0) vm_wait<LDX>();
+    else vm_wait<LDX + ST>();
     const int tile = slot + it * step;
     char* yimg = smem + (it & 1) * IMG_Y;
     const char* xim = ximg + (it % 3) * IMG_X;
     if constexpr (YR) {
       // every wave's X share landed; every wave is done with the previous tile's y stage
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      lds_barrier();
       // (in two halves of 32 pixels: half the accumulators)
 #pragma unroll
       for (int hp = 0; hp < 2; ++hp) {
@@ -515,9 +430,8 @@ __global__ void __launch_bounds__(256, 1) pw_bwd_bn_kernel(PbnArgs A) {
           v8bf xa[2];
 #pragma unroll
           for (int i = 0; i < 2; ++i) xa[i] = row_frag<CB>(xim, 32 * hp + 16 * i, kk, lane);
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-          for (int i = 0; i < 2; ++i) asm volatile("" : "+v"(xa[i]));
+          lds_wait();
+          tie(xa);
 #pragma unroll
           for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -532,16 +446,15 @@ __global__ void __launch_bounds__(256, 1) pw_bwd_bn_kernel(PbnArgs A) {
             o.x = pack2bf(ay[i][j][0], ay[i][j][1]);
             o.y = pack2bf(ay[i][j][2], ay[i][j][3]);
             const int pl = 32 * hp + 16 * i + (lane & 15), kl = 64 * wave + 16 * j + 4 * (lane >> 4);
-            const uint32_t addr = (uint32_t)(uintptr_t)LDS_PTR(char, ystg + (pl * YROW + kl) * 2);
-            asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(o) : "memory");
+            lds_store8(ystg + (pl * YROW + kl) * 2, o);
           }
       }
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // y staged
+      lds_barrier();  // y staged
     }
     transform(tile, yimg);
     // every wave's dY share is written, every wave's X share landed; every wave is done with the dY image and the X
     // buffer that this iteration's loads below refill
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    lds_barrier();
     uint4 xv[ST];
     uint32_t xmb[ST];
 #pragma unroll
@@ -549,8 +462,8 @@ __global__ void __launch_bounds__(256, 1) pw_bwd_bn_kernel(PbnArgs A) {
       const int p = tile * BMP + ((t + 256 * k) / CH);
       const uint32_t e = (uint32_t)p * C + nch;
       const bool ok = p < a.P;
-      xv[k] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(xbr, ok ? e * 2u : 0x80000000u, 0, 0));
-      xmb[k] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(xmr, ok ? e >> 3 : 0x80000000u, 0, 0);
+      xv[k] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(xbr, ok ? e * 2u : OOB_OFF, 0, 0));
+      xmb[k] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(xmr, ok ? e >> 3 : OOB_OFF, 0, 0);
     }
     load_tile(tile_of(it + 1));
     x_issue(tile_of(it + 2), ximg + ((it + 2) % 3) * IMG_X);
@@ -560,14 +473,12 @@ __global__ void __launch_bounds__(256, 1) pw_bwd_bn_kernel(PbnArgs A) {
     for (int kk = 0; kk < NKK; ++kk) {
       v8bf fx[4], fy[FK];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) fx[i] = tr_frag<CB>(xim, 16 * i, kk, lane);
+      for (int i = 0; i < 4; ++i) fx[i] = frag_kouter_async<CB>(xim, 16 * i, kk, lane);
 #pragma unroll
-      for (int j = 0; j < FK; ++j) fy[j] = tr_frag<K>(yimg, (K / 4) * wave + 16 * j, kk, lane);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(fx[i]));
-#pragma unroll
-      for (int j = 0; j < FK; ++j) asm volatile("" : "+v"(fy[j]));
+      for (int j = 0; j < FK; ++j) fy[j] = frag_kouter_async<K>(yimg, (K / 4) * wave + 16 * j, kk, lane);
+      lds_wait();
+      tie(fx);
+      tie(fy);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -582,9 +493,8 @@ __global__ void __launch_bounds__(256, 1) pw_bwd_bn_kernel(PbnArgs A) {
       v8bf fa[FP];
 #pragma unroll
       for (int i = 0; i < FP; ++i) fa[i] = row_frag<K>(yimg, 16 * i, s, lane);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int i = 0; i < FP; ++i) asm volatile("" : "+v"(fa[i]));
+      lds_wait();
+      tie(fa);
 #pragma unroll
       for (int i = 0; i < FP; ++i) ad[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[s], fa[i], ad[i], 0, 0, 0);
     }
@@ -594,26 +504,19 @@ __global__ void __launch_bounds__(256, 1) pw_bwd_bn_kernel(PbnArgs A) {
       uint2 o;
       o.x = pack2bf(ad[i][0], ad[i][1]);
       o.y = pack2bf(ad[i][2], ad[i][3]);
-      const uint32_t addr = (uint32_t)(uintptr_t)LDS_PTR(char, stg + (pl * SROW + cl) * 2);
-      asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(o) : "memory");
+      lds_store8(stg + (pl * SROW + cl) * 2, o);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // the tile is staged
+    lds_barrier();  // the tile is staged
     // the BN loads are in: issued after them, the next tile's registers (LR) and X image (LDX)
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LR + LDX) : "memory");
+    vm_wait<LR + LDX>();
 #pragma unroll
     for (int k = 0; k < ST; ++k) {
       const int pl = (t + 256 * k) / CH;
       const int p = tile * BMP + pl;
-      uint4 val;
-      {
-        const uint32_t addr = (uint32_t)(uintptr_t)LDS_PTR(char, stg + (pl * SROW + ch * 8) * 2);
-        v4i r;
-        asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(r) : "v"(addr) : "memory");
-        val = __builtin_bit_cast(uint4, r);
-      }
+      const uint4 val = lds_load16(stg + (pl * SROW + ch * 8) * 2);
       const bool ok = p < a.P;
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, val), dxr,
-                                             ok ? ((uint32_t)p * C + nch) * 2u : 0x80000000u, 0, 0);
+                                             ok ? ((uint32_t)p * C + nch) * 2u : OOB_OFF, 0, 0);
       const uint32_t bits = ok ? (xmb[k] | xm_or) : 0u;
       const uint32_t vw[4] = {val.x, val.y, val.z, val.w}, xw[4] = {xv[k].x, xv[k].y, xv[k].z, xv[k].w};
 #pragma unroll
@@ -639,7 +542,7 @@ __global__ void __launch_bounds__(256, 1) pw_bwd_bn_kernel(PbnArgs A) {
       const int c = c0 + 16 * i + 4 * (lane >> 4);
       *reinterpret_cast<float4*>(slab + (long)k * C + c) = make_float4(aw[i][j][0], aw[i][j][1], aw[i][j][2], aw[i][j][3]);
     }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the dummy loads / DMA past the last tile have landed too
+  vm_wait<0>();  // the dummy loads / DMA past the last tile have landed too
   if constexpr (SC) {  // the shortcut's partial row: the RPT threads of each dY chunk folded in a fixed order
     __syncthreads();
     float* red2 = reinterpret_cast<float*>(smem);

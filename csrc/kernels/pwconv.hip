@@ -9,8 +9,8 @@
 //    blocks that share A rows for the N/256 column tiles sit on one XCD), so the block's whole weight slice
 //    (64 columns x C_in per wave, <= 128 VGPRs) is loaded into REGISTERS once and never staged again;
 //  * only A (the activation tile, BM x C_in) streams through LDS, by LDS-DMA into a 3-deep ring: the next two
-//    tiles are in flight while this one is multiplied and stored, counted vmcnt waits (stores are issued
-//    unconditionally — rows past M go to an out-of-range buffer offset — so the count is exact);
+//    tiles are in flight while this one is multiplied and stored (the lds_async.h discipline: counted vmcnt waits,
+//    stores issued unconditionally — rows past M go to an out-of-range buffer offset — so the count is exact);
 //  * the epilogue stores bf16 straight from the accumulators and keeps the BN sum / sum-of-squares of the
 //    stored (bf16) values in registers across ALL of the block's tiles: one partial row per block (<= 256 rows).
 // Two-pass ConvBN forward (MODE 1 then MODE 2, dtf_conv_bn_apply_fwd): the layer writes 4x the bytes it reads, so
@@ -21,13 +21,11 @@
 // conv output yc only when the backward still needs it) — the standalone apply pass (read yc + res, write out) and
 // the yc write/read disappear (ResNet-50 bottleneck c3: 17 -> 14 activation-widths of traffic, 10 without yc).
 // Reference op: the Conv2D + FusedBatchNorm pair of the model trainer/task.py:62-71 builds.
-#include "gemm_core.h"
+#include "lds_async.h"
+#include "routes.h"
 
 namespace dtf {
 namespace {
-
-typedef int v2i __attribute__((ext_vector_type(2)));
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 struct PwArgs {
   const bf16_t* X;  // [M][C] activations
@@ -85,40 +83,6 @@ struct PwGeo {
   static constexpr int STM = MODE == 1 ? 0 : ST;
 };
 
-// One 8-B fragment into the LDS store stage. Inline asm on purpose: the compiler cannot tell the stage from the DMA
-// ring (LDS-DMA writes carry no alias information), so before a plain LDS store it waits for EVERY outstanding
-// vector-memory op — draining the DMA of the tile two ahead before each epilogue and leaving one tile of prefetch.
-// The stage never overlaps the ring; tile_barrier() waits for these writes before it publishes the tile.
-__device__ __forceinline__ void stage_write(char* p, uint2 v) {
-  const uint32_t addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)p;
-  asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
-
-// Workgroup barrier for the tile loop: this thread's LDS ops done, then s_barrier, as one asm statement (a compiler
-// memory barrier too). __syncthreads()' fence makes the compiler drain every outstanding vector-memory op first (it
-// counts the in-flight LDS-DMA of the next tiles as pending LDS writes); the loop orders its DMA with explicit vmcnt
-// waits instead.
-__device__ __forceinline__ void tile_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// N 16-B chunks of the LDS store stage (byte offsets off[i] from base), by inline asm for the same reason as
-// stage_write: a plain LDS load here makes hipcc drain the DMA of the tile two ahead ("s_waitcnt vmcnt(0)") before the
-// store pass of every tile. One wait for all N reads; each result is tied to it.
-template <int N>
-__device__ __forceinline__ void stage_read(uint4 (&v)[N], const char* base, const int (&off)[N]) {
-  v4i r[N];
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    const uint32_t addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)(base + off[i]);
-    asm volatile("ds_read_b128 %0, %1" : "=v"(r[i]) : "v"(addr));
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    asm volatile("" : "+v"(r[i]));
-    v[i] = __builtin_bit_cast(uint4, r[i]);
-  }
-}
-
 template <int C, int WMW, bool STG, int MODE, bool RX = false>
 __global__ void __launch_bounds__(256 * WMW, 1) pw_conv_kernel(PwArgs a) {
   static_assert(MODE < 2 || STG, "the apply / data-gradient epilogues work on the LDS-staged tile");
@@ -149,10 +113,8 @@ __global__ void __launch_bounds__(256 * WMW, 1) pw_conv_kernel(PwArgs a) {
                                                   8 * (lane >> 4));
 
   // ---- A tile DMA (lane-linear [BM][64] sub-images, source-side XOR swizzle undone by frag_kcontig)
-  const __amdgpu_buffer_rsrc_t xr =
-      __builtin_amdgcn_make_buffer_rsrc((void*)a.X, (short)0, (int)((long)a.M * C * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t yr =
-      __builtin_amdgcn_make_buffer_rsrc((void*)a.Y, (short)0, (int)((long)a.M * a.K * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t xr = buf_rsrc(a.X, (int)((long)a.M * C * 2));
+  const __amdgpu_buffer_rsrc_t yr = buf_rsrc(a.Y, (int)((long)a.M * a.K * 2));
   auto issue = [&](int mt, int buf) {
     char* img = smem + buf * G::IMG;
 #pragma unroll
@@ -160,19 +122,16 @@ __global__ void __launch_bounds__(256 * WMW, 1) pw_conv_kernel(PwArgs a) {
       const int row = G::RPI * i + (t >> 3);
       const int r = mt * G::BM + row;
       const uint32_t base = r < a.M ? (uint32_t)r * (uint32_t)(C * 2) + (uint32_t)(((t & 7) ^ ((row >> 1) & 7)) * 16)
-                                    : 0x80000000u;
+                                    : OOB_OFF;
 #pragma unroll
       for (int kt = 0; kt < G::NKT; ++kt)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            xr, (__attribute__((address_space(3))) void*)(img + kt * G::SUB + i * (G::RPI * 128) + wave * 1024), 16,
-            base + kt * 128, 0, 0, 0);
+        dma16(xr, img + kt * G::SUB + i * (G::RPI * 128) + wave * 1024, base + kt * 128);
     }
   };
 
   // RX: the recompute operands — the wave's rw slice in registers (rows n0 + 16 j + (lane & 15)), rx tiles by DMA
   v8bf fr[RX ? 4 : 1][2];
-  const __amdgpu_buffer_rsrc_t rxr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)a.rx, (short)0, RX ? (int)((long)a.M * 128) : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rxr = buf_rsrc(a.rx, RX ? (int)((long)a.M * 128) : 0);
   if constexpr (RX) {
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -191,9 +150,8 @@ __global__ void __launch_bounds__(256 * WMW, 1) pw_conv_kernel(PwArgs a) {
         const int row = G::RPI * i + (t >> 3);
         const int r = mt * G::BM + row;
         const uint32_t base =
-            r < a.M ? (uint32_t)r * 128u + (uint32_t)(((t & 7) ^ ((row >> 1) & 7)) * 16) : 0x80000000u;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            rxr, (__attribute__((address_space(3))) void*)(img + i * (G::RPI * 128) + wave * 1024), 16, base, 0, 0, 0);
+            r < a.M ? (uint32_t)r * 128u + (uint32_t)(((t & 7) ^ ((row >> 1) & 7)) * 16) : OOB_OFF;
+        dma16(rxr, img + i * (G::RPI * 128) + wave * 1024, base);
       }
     }
   };
@@ -216,6 +174,7 @@ __global__ void __launch_bounds__(256 * WMW, 1) pw_conv_kernel(PwArgs a) {
   const int ch = t & 31;
   const int nch = tile_n * 256 + ch * 8;
   float bsc[8], bsh[8], rsc[8], rsh[8];
+  // (the builtin itself for these three: through buf_rsrc hipcc orders the MODE 2 kernels' scalar code differently)
   const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
       (void*)a.res, (short)0, (MODE == 2 && a.res) ? (int)((long)a.M * a.K * 2) : 0, 0x00020000);
   const __amdgpu_buffer_rsrc_t orr = __builtin_amdgcn_make_buffer_rsrc(
@@ -224,14 +183,11 @@ __global__ void __launch_bounds__(256 * WMW, 1) pw_conv_kernel(PwArgs a) {
       (void*)a.mbits, (short)0, (MODE == 2 && a.mbits) ? (int)((long)a.M * a.K / 8) : 0, 0x00020000);
   // MODE 3: the old values (beta source), the BN input and its mask, the batch mean of this thread's 8 channels, and the
   // thread's running sums of dz and dz * (x - mean) over all of its rows
-  const __amdgpu_buffer_rsrc_t cr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)a.cin, (short)0, (MODE == 3 && a.cin) ? (int)((long)(a.bW ? a.M / 4 : a.M) * a.K * 2) : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t xbr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)a.bnx, (short)0, (MODE == 3 && a.bnmean && !RX) ? (int)((long)a.M * a.K * 2) : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t bmr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)a.betamask, (short)0, (MODE == 3 && a.betamask) ? (int)((long)a.M * a.K / 8) : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t xmr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)a.bnmask, (short)0, (MODE == 3 && a.bnmask) ? (int)((long)a.M * a.K / 8) : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t cr =
+      buf_rsrc(a.cin, (MODE == 3 && a.cin) ? (int)((long)(a.bW ? a.M / 4 : a.M) * a.K * 2) : 0);
+  const __amdgpu_buffer_rsrc_t xbr = buf_rsrc(a.bnx, (MODE == 3 && a.bnmean && !RX) ? (int)((long)a.M * a.K * 2) : 0);
+  const __amdgpu_buffer_rsrc_t bmr = buf_rsrc(a.betamask, (MODE == 3 && a.betamask) ? (int)((long)a.M * a.K / 8) : 0);
+  const __amdgpu_buffer_rsrc_t xmr = buf_rsrc(a.bnmask, (MODE == 3 && a.bnmask) ? (int)((long)a.M * a.K / 8) : 0);
   const uint32_t bm_or = a.betamask ? 0u : 0xFFu, xm_or = a.bnmask ? 0u : 0xFFu;  // absent mask: every bit set
   float mu3[8], s3[8], q3[8];
 #pragma unroll
@@ -270,16 +226,16 @@ __global__ void __launch_bounds__(256 * WMW, 1) pw_conv_kernel(PwArgs a) {
     // and tile it-1's stores. MODE 1: only tile it+1's DMA. MODE 2 / 3: tile `it` is older than tile it-1's loads,
     // which iteration it-1 waited for — only the first tile needs a wait here.
     if constexpr (MODE == 0) {
-      if (it == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::LD) : "memory");
-      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::LD + G::ST) : "memory");
+      if (it == 0) vm_wait<G::LD>();
+      else vm_wait<G::LD + G::ST>();
     } else if constexpr (MODE == 1) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::LD) : "memory");
+      vm_wait<G::LD>();
     } else {  // MODE 2 / 3
       if (it == 0) {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LDT) : "memory");
+        vm_wait<LDT>();
       }
     }
-    tile_barrier();  // every wave's DMA share landed; every wave is done with the buffer tile it+2 reuses
+    lds_barrier();  // every wave's DMA share landed; every wave is done with the buffer tile it+2 reuses
     const int mt = first + it * step;
     // MODE 2: this tile's residual chunks, in flight under the MFMAs (issued before tile it+2's DMA, so waiting for
     // them leaves that DMA in flight)
@@ -296,8 +252,8 @@ __global__ void __launch_bounds__(256 * WMW, 1) pw_conv_kernel(PwArgs a) {
         const int row = (t + k * G::NTH) >> 5;
         const int m = mt * G::BM + row;
         const uint32_t e = (uint32_t)m * (uint32_t)a.K + (uint32_t)nch;
-        off[k] = m < a.M ? e * 2u : 0x80000000u;
-        boff[k] = m < a.M ? e >> 3 : 0x80000000u;
+        off[k] = m < a.M ? e * 2u : OOB_OFF;
+        boff[k] = m < a.M ? e >> 3 : OOB_OFF;
         coff[k] = off[k];
         cbits[k] = 0xFFu;
         if (a.bW) {  // compact stride-2 source: even pixels only
@@ -306,7 +262,7 @@ __global__ void __launch_bounds__(256 * WMW, 1) pw_conv_kernel(PwArgs a) {
           const bool even = m < a.M && !((h | w) & 1u);
           coff[k] = even ? (((img * (uint32_t)(a.bH / 2) + (h >> 1)) * (uint32_t)(a.bW / 2) + (w >> 1)) *
                                 (uint32_t)a.K + (uint32_t)nch) * 2u
-                         : 0x80000000u;
+                         : OOB_OFF;
           cbits[k] = even ? 0xFFu : 0u;
         }
       }
@@ -325,7 +281,7 @@ __global__ void __launch_bounds__(256 * WMW, 1) pw_conv_kernel(PwArgs a) {
       for (int k = 0; k < G::ST; ++k) {
         const int row = (t + k * G::NTH) >> 5;
         const int m = mt * G::BM + row;
-        const uint32_t off = m < a.M ? ((uint32_t)m * (uint32_t)a.K + (uint32_t)nch) * 2u : 0x80000000u;
+        const uint32_t off = m < a.M ? ((uint32_t)m * (uint32_t)a.K + (uint32_t)nch) * 2u : OOB_OFF;
         rv[k] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rr, off, 0, 0));
       }
     }
@@ -368,10 +324,10 @@ __global__ void __launch_bounds__(256 * WMW, 1) pw_conv_kernel(PwArgs a) {
         if constexpr (STG) {
           if constexpr (MODE != 1) {
             const int ml = wm * 64 + 16 * i + (lane & 15), nl = wn * 64 + 16 * j + 4 * (lane >> 4);
-            stage_write(stg + (ml * G::SROW + nl) * 2, o);
+            lds_store8(stg + (ml * G::SROW + nl) * 2, o);
           }
         } else if constexpr (MODE != 1) {
-          const uint32_t off = m < a.M ? ((uint32_t)m * (uint32_t)a.K + (uint32_t)n) * 2u : 0x80000000u;
+          const uint32_t off = m < a.M ? ((uint32_t)m * (uint32_t)a.K + (uint32_t)n) * 2u : OOB_OFF;
           __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2i, o), yr, off, 0, 0);
         }
         if constexpr (MODE < 2) {
@@ -386,38 +342,38 @@ __global__ void __launch_bounds__(256 * WMW, 1) pw_conv_kernel(PwArgs a) {
       }
     }
     if constexpr (STG && MODE == 0) {
-      tile_barrier();  // the tile is staged (the next tile's staging writes come after the next top barrier)
+      lds_barrier();  // the tile is staged (the next tile's staging writes come after the next top barrier)
       uint4 sv[G::ST];
       int so[G::ST];
 #pragma unroll
       for (int k = 0; k < G::ST; ++k) so[k] = (((t + k * G::NTH) >> 5) * G::SROW + ((t + k * G::NTH) & 31) * 8) * 2;
-      stage_read(sv, stg, so);
+      lds_load16(sv, stg, so);
 #pragma unroll
       for (int k = 0; k < G::ST; ++k) {
         const int c = t + k * G::NTH, row = c >> 5, ch = c & 31;
         const int m = mt * G::BM + row;
         const uint4 v = sv[k];
         const uint32_t off =
-            m < a.M ? ((uint32_t)m * (uint32_t)a.K + (uint32_t)(tile_n * 256 + ch * 8)) * 2u : 0x80000000u;
+            m < a.M ? ((uint32_t)m * (uint32_t)a.K + (uint32_t)(tile_n * 256 + ch * 8)) * 2u : OOB_OFF;
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, v), yr, off, 0, 0);
       }
     }
     if constexpr (MODE == 2) {
-      tile_barrier();  // the tile is staged
+      lds_barrier();  // the tile is staged
       // the residual chunks are in: everything but tile it+2's DMA (issued after them) has completed
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::LD) : "memory");
+      vm_wait<G::LD>();
       uint4 sv[G::ST];
       int so[G::ST];
 #pragma unroll
       for (int k = 0; k < G::ST; ++k) so[k] = (((t + k * G::NTH) >> 5) * G::SROW + ch * 8) * 2;
-      stage_read(sv, stg, so);
+      lds_load16(sv, stg, so);
 #pragma unroll
       for (int k = 0; k < G::ST; ++k) {
         const int row = (t + k * G::NTH) >> 5;
         const int m = mt * G::BM + row;
         const uint4 yv = sv[k];
         const uint32_t e = (uint32_t)m * (uint32_t)a.K + (uint32_t)nch;  // element index (valid rows)
-        const uint32_t off = m < a.M ? e * 2u : 0x80000000u;
+        const uint32_t off = m < a.M ? e * 2u : OOB_OFF;
         if (a.Y) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, yv), yr, off, 0, 0);
         // bn_apply_row's arithmetic, operation for operation (bitwise the same block output)
         const uint32_t yw[4] = {yv.x, yv.y, yv.z, yv.w};
@@ -444,7 +400,7 @@ __global__ void __launch_bounds__(256 * WMW, 1) pw_conv_kernel(PwArgs a) {
           uint32_t bits = 0;
 #pragma unroll
           for (int j = 0; j < 8; ++j) bits |= (uint32_t)(f2bf(o[j]) != 0 && o[j] > 0.f) << j;
-          __builtin_amdgcn_raw_buffer_store_b8((uint8_t)bits, mr, m < a.M ? e >> 3 : 0x80000000u, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b8((uint8_t)bits, mr, m < a.M ? e >> 3 : OOB_OFF, 0, 0);
         }
       }
     }
@@ -475,21 +431,21 @@ __global__ void __launch_bounds__(256 * WMW, 1) pw_conv_kernel(PwArgs a) {
             uint2 o;
             o.x = pack2bf(ay[i][j][0], ay[i][j][1]);
             o.y = pack2bf(ay[i][j][2], ay[i][j][3]);
-            stage_write(ystg + ((16 * i + (lane & 15)) * YROW + wn * 64 + 16 * j + 4 * (lane >> 4)) * 2, o);
+            lds_store8(ystg + ((16 * i + (lane & 15)) * YROW + wn * 64 + 16 * j + 4 * (lane >> 4)) * 2, o);
           }
       }
-      tile_barrier();  // the tile is staged (RX: and its BN input)
+      lds_barrier();  // the tile is staged (RX: and its BN input)
       // the tile's loads are in: everything but tile it+2's DMA (issued after them) has completed
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LDT) : "memory");
+      vm_wait<LDT>();
       uint4 sv[G::ST];
       int so[G::ST];
 #pragma unroll
       for (int k = 0; k < G::ST; ++k) so[k] = (((t + k * G::NTH) >> 5) * G::SROW + ch * 8) * 2;
-      stage_read(sv, stg, so);
+      lds_load16(sv, stg, so);
       if constexpr (RX) {
 #pragma unroll
         for (int k = 0; k < G::ST; ++k) so[k] = (((t + k * G::NTH) >> 5) * YROW + ch * 8) * 2;
-        stage_read(xv, ystg, so);
+        lds_load16(xv, ystg, so);
       }
 #pragma unroll
       for (int k = 0; k < G::ST; ++k) {
@@ -508,7 +464,7 @@ __global__ void __launch_bounds__(256 * WMW, 1) pw_conv_kernel(PwArgs a) {
           for (int r = 0; r < 8; ++r) f[r] = ((bmb[k] >> r) & 1u) ? fmaf(a.beta, g[r], f[r]) : f[r];
           val = make_uint4(pack2bf(f[0], f[1]), pack2bf(f[2], f[3]), pack2bf(f[4], f[5]), pack2bf(f[6], f[7]));
         }
-        const uint32_t off = m < a.M ? ((uint32_t)m * (uint32_t)a.K + (uint32_t)nch) * 2u : 0x80000000u;
+        const uint32_t off = m < a.M ? ((uint32_t)m * (uint32_t)a.K + (uint32_t)nch) * 2u : OOB_OFF;
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, val), yr, off, 0, 0);
         {  // (unconditional: with no bnmean the sums are of zeros and never written; a branch here leaves the xv
            // loads unconsumed on one path, and the compiler then drains every load before the next tile's)
@@ -530,7 +486,7 @@ __global__ void __launch_bounds__(256 * WMW, 1) pw_conv_kernel(PwArgs a) {
   }
   // the dummy DMA past the last tile (and, for blocks without tiles, both prologue ones) lands in the ring before it
   // is reused below
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  vm_wait<0>();
   if constexpr (MODE == 2) return;  // (no statistics)
   if constexpr (MODE == 3) {
     if (!a.bnmean) return;
@@ -679,10 +635,6 @@ int pwconv_dgrad_try(const void* dY, const void* Wck, void* dX, float beta, cons
 }
 
 }  // namespace dtf
-
-DTF_API int dtf_bn_finalize(float* part, int T, const float* gamma, const float* beta, float* running_mean,
-                            float* running_var, long M, int C, float momentum, float eps, float* scale,
-                            float* shift, float* mean_out, float* invstd_out, void* stream);  // norm.hip
 
 // Two-pass training ConvBN forward of a channel-expanding 1x1 conv (see the MODE notes at the top):
 //   pass 1: statistics of yc = X W^T (nothing stored) -> part;  finalize -> scale/shift/mean/invstd + running stats;

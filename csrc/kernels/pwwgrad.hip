@@ -7,14 +7,14 @@
 //    output tile (KT x CT, <= 32 K floats) lives in the accumulators for the entire pixel range, so nothing but the
 //    operands moves until one f32 partial per block is written at the end;
 //  * both operands stream through a 3-deep LDS-DMA ring as K-outer images (the pixel is the reduction index, so
-//    the MFMA fragments are read transposed with ds_read_b64_tr_b16, frag_kouter's addressing); the tile two ahead
-//    stays in flight under the MFMAs of this one (explicit vmcnt waits; the transposed reads and the barrier are
-//    inline asm so the compiler does not drain the DMA before them, as gemm_w4.hip does);
+//    the MFMA fragments are read transposed with ds_read_b64_tr_b16); the tile two ahead stays in flight under the
+//    MFMAs of this one (the lds_async.h discipline);
 //  * blocks that share a pixel range (output tiles of a filter larger than one block tile) sit on one XCD, whose L2
 //    then serves the operand they share.
 // The partials ([splits][K][C] f32) are summed in a fixed order by dtf_sum_rows (deterministic, no atomics).
 // Reference op: the Conv2D weight gradient of the model trainer/task.py:62-71 builds.
-#include "gemm_core.h"
+#include "lds_async.h"
+#include "routes.h"
 
 namespace dtf {
 namespace {
@@ -25,56 +25,6 @@ struct WgArgs {
   float* ws;         // [splits][K][C] partials
   int P, K, C;
   int tiles_p, tiles_c, n_out, splits;
-};
-
-// transposed fragment of a [64 pixel][R] K-outer image: columns cb..cb+15 (lane & 15), pixel substep kk
-template <int R>
-__device__ __forceinline__ v8bf wg_frag(const char* lds, int cb, int kk, int lane) {
-  const int G = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-  v4s r[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int k = 32 * kk + 8 * G + 4 * h + q;
-    const int g = ((cb >> 2) + p) ^ (kouter_swz<R>(k) << 2);
-    const uint32_t addr = (uint32_t)(uintptr_t)LDS_PTR(char, lds + k * (R * 2) + g * 8);
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r[h]) : "v"(addr));
-  }
-  v8s both = __builtin_shufflevector(r[0], r[1], 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(v8bf, both);
-}
-
-// LDS-DMA of one operand's [64 pixel][R] slice (columns col0 .. col0+R of rows with stride ld elements) into the
-// K-outer image: 256 threads x 16 B per wave-instruction set, each lane fetching the logical chunk that the XOR
-// swizzle puts at its physical slot (GldsKOuter's mapping); pixels past P read zeros through the range check
-template <int R>
-struct WgOperand {
-  static constexpr int L = R / 32;  // DMA instructions per thread per tile
-  __amdgpu_buffer_rsrc_t rsrc;
-  int kr[L], coff[L], rowb;
-
-  __device__ __forceinline__ void init(const bf16_t* p, long rows, int ld, int col0) {
-    const int t = threadIdx.x;
-    rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, (int)(rows * ld * 2), 0x00020000);
-    rowb = ld * 2;
-#pragma unroll
-    for (int i = 0; i < L; ++i) {
-      const int pb = i * 4096 + t * 16;
-      kr[i] = pb / (R * 2);
-      const int c = ((pb % (R * 2)) >> 4) ^ (kouter_swz<R>(kr[i]) << 1);
-      coff[i] = (col0 + c * 8) * 2;
-    }
-  }
-
-  __device__ __forceinline__ void issue(int p0, int P, char* lds) {
-    const int wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < L; ++i) {
-      const int p = p0 + kr[i];
-      const uint32_t off = p < P ? (uint32_t)(p * rowb + coff[i]) : 0x80000000u;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          rsrc, (__attribute__((address_space(3))) void*)(lds + i * 4096 + wave * 1024), 16, off, 0, 0, 0);
-    }
-  }
 };
 
 // KT x CT output tile per block; WKR waves along k (the rest along c): wave tile (KT/WKR) x (CT*WKR/4)
@@ -96,8 +46,8 @@ __global__ void __launch_bounds__(256, 1) pw_wgrad_kernel(WgArgs a) {
   const int slot = xcd + 8 * (j8 / a.n_out);
   const int k0 = (o / a.tiles_c) * KT, c0 = (o % a.tiles_c) * CT;
 
-  WgOperand<KT> opy;
-  WgOperand<CT> opx;
+  KOuterDma<KT> opy;
+  KOuterDma<CT> opx;
   opy.init(a.dY, a.P, a.K, k0);
   opx.init(a.X, a.P, a.C, c0);
   auto issue = [&](int tile, int buf) {
@@ -119,26 +69,23 @@ __global__ void __launch_bounds__(256, 1) pw_wgrad_kernel(WgArgs a) {
 
   for (int it = 0; it < n_mine; ++it) {
     // tile `it` landed: the ops this thread issued after it are tile it+1's DMA (if any)
-    if (it + 1 < n_mine) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LD) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (it + 1 < n_mine) vm_wait<LD>();
+    else vm_wait<0>();
     // every wave's share landed; every wave is done with the buffer tile it+2 reuses (its reads were waited for
     // before the MFMAs that consumed them)
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    lds_barrier();
     if (it + 2 < n_mine) issue(slot + (it + 2) * step, (it + 2) % NBUF);
     const char* img = smem + (it % NBUF) * IMG;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
       v8bf fx[FC], fy[FK];
 #pragma unroll
-      for (int i = 0; i < FC; ++i) fx[i] = wg_frag<CT>(img + IMG_Y, wc * WC + 16 * i, kk, lane);
+      for (int i = 0; i < FC; ++i) fx[i] = frag_kouter_async<CT>(img + IMG_Y, wc * WC + 16 * i, kk, lane);
 #pragma unroll
-      for (int j = 0; j < FK; ++j) fy[j] = wg_frag<KT>(img, wk * WK + 16 * j, kk, lane);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      // (the asm reads' results exist only after that wait: tie every fragment to it)
-#pragma unroll
-      for (int i = 0; i < FC; ++i) asm volatile("" : "+v"(fx[i]));
-#pragma unroll
-      for (int j = 0; j < FK; ++j) asm volatile("" : "+v"(fy[j]));
+      for (int j = 0; j < FK; ++j) fy[j] = frag_kouter_async<KT>(img, wk * WK + 16 * j, kk, lane);
+      lds_wait();
+      tie(fx);
+      tie(fy);
       // D[c][k] (lane: 4 consecutive c of one k): src0 X^T rows = c, src1 dY columns = k
 #pragma unroll
       for (int i = 0; i < FC; ++i)

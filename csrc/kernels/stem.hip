@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "routes.h"
 
 namespace {
 

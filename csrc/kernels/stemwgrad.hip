@@ -14,13 +14,11 @@
 //  * a tap (a, b) is a pixel shift: the B fragment of tap b is the transposed read of pixels k + b of the wave's s2d
 //    row, so no im2col image exists anywhere. s2d row slots are 32-B pixel rows with bit 2 of the pixel index
 //    flipped by its bit 3 (the rows k and k + 8 of a transposed read then sit on different banks).
-// The LDS reads and the barrier are inline asm with explicit waits (the pwwgrad.hip discipline: hipcc must not drain
-// the in-flight DMA before them); every thread issues exactly 8 DMA pieces per row (unneeded s2d rows go to a junk
-// area with an out-of-range offset), so the vmcnt of "one row still in flight" is a constant.
+// The lds_async.h discipline: every thread issues exactly 8 DMA pieces per row (unneeded s2d rows go to a junk area
+// with an out-of-range offset), so the vmcnt of "one row still in flight" is a constant.
 // Reference op: the Conv2D weight gradient of the model trainer/task.py:62-71 builds.
-#include <cstdlib>
-
-#include "gemm_core.h"
+#include "lds_async.h"
+#include "routes.h"
 
 namespace dtf {
 namespace {
@@ -43,26 +41,7 @@ struct SwArgs {
 
 __device__ __forceinline__ int sw_px(int x) { return x ^ ((x >> 1) & 4); }
 
-__device__ __forceinline__ v8bf tr_pair(uint32_t a0, uint32_t a1) {
-  v4s r0, r1;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r0) : "v"(a0));
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r1) : "v"(a1));
-  v8s both = __builtin_shufflevector(r0, r1, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(v8bf, both);
-}
-// dY^T fragment: out channels cb..cb+15, pixels of k-step ks (frag_kouter's slot order, kouter_swz<64> image)
-__device__ __forceinline__ v8bf dy_frag(const char* img, int cb, int ks, int lane) {
-  const int G = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-  uint32_t ad[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int k = 32 * ks + 8 * G + 4 * h + q;
-    const int g = ((cb >> 2) + p) ^ (kouter_swz<64>(k) << 2);
-    ad[h] = (uint32_t)(uintptr_t)LDS_PTR(char, img + k * 128 + g * 8);
-  }
-  return tr_pair(ad[0], ad[1]);
-}
-// s2d fragment of tap column b: the 16 channels of pixels k + b (the same pixel slot order as dy_frag)
+// s2d fragment of tap column b: the 16 channels of pixels k + b (frag_kouter_async's pixel slot order)
 __device__ __forceinline__ v8bf s2d_frag(const char* srow, int b, int ks, int lane) {
   const int G = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
   uint32_t ad[2];
@@ -106,19 +85,17 @@ __global__ void __launch_bounds__(256, 1) stem_wgrad_kernel(SwArgs a) {
     doff[i] = dkr[i] * 128 + c * 16;
   }
   const int sx = sw_px(t >> 1);
-  const uint32_t soff = sx < a.Ws ? (uint32_t)(sx * 32 + (t & 1) * 16) : 0x80000000u;
+  const uint32_t soff = sx < a.Ws ? (uint32_t)(sx * 32 + (t & 1) * 16) : OOB_OFF;
 
   // output rows are walked with incremental (n, h) counters: no 64-bit division per row
   auto issue = [&](int it, int n, int h) {
     const long r = r0 + it;
-    const __amdgpu_buffer_rsrc_t ry =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(a.dY + r * a.Q * 64), (short)0, a.Q * 128, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ry = buf_rsrc(a.dY + r * a.Q * 64, a.Q * 128);
     char* img = dyi + (it % SW_NB) * SW_DY;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const uint32_t off = dkr[i] < a.Q ? (uint32_t)doff[i] : 0x80000000u;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          ry, (__attribute__((address_space(3))) void*)(img + i * 4096 + wave * 1024), 16, off, 0, 0, 0);
+      const uint32_t off = dkr[i] < a.Q ? (uint32_t)doff[i] : OOB_OFF;
+      dma16(ry, img + i * 4096 + wave * 1024, off);
     }
     // s2d rows h .. h+3 of image n: all four at the block's first row and at an image's first row, else h + 3
     const int first = (it == 0 || h == 0) ? 0 : 3;
@@ -126,11 +103,9 @@ __global__ void __launch_bounds__(256, 1) stem_wgrad_kernel(SwArgs a) {
     for (int j = 0; j < 4; ++j) {
       const long L = (long)n * a.Hs + h + j;
       const bool need = j >= first;
-      const __amdgpu_buffer_rsrc_t rx =
-          __builtin_amdgcn_make_buffer_rsrc((void*)(a.X + L * a.Ws * 16), (short)0, a.Ws * 32, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rx = buf_rsrc(a.X + L * a.Ws * 16, a.Ws * 32);
       char* dst = need ? s2d + (int)(L & (SW_NS - 1)) * SW_SLOT : junk;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          rx, (__attribute__((address_space(3))) void*)(dst + wave * 1024), 16, need ? soff : 0x80000000u, 0, 0, 0);
+      dma16(rx, dst + wave * 1024, need ? soff : OOB_OFF);
     }
   };
 
@@ -156,12 +131,12 @@ __global__ void __launch_bounds__(256, 1) stem_wgrad_kernel(SwArgs a) {
 
   for (int it = 0; it < n_mine; ++it) {
     // row `it` landed: what this thread issued after it are rows it+1 .. it+NB-2 (8 pieces each, when they exist)
-    if (NB >= 5 && it + 3 < n_mine) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-    else if (NB >= 4 && it + 2 < n_mine) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else if (it + 1 < n_mine) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (NB >= 5 && it + 3 < n_mine) vm_wait<24>();
+    else if (NB >= 4 && it + 2 < n_mine) vm_wait<16>();
+    else if (it + 1 < n_mine) vm_wait<8>();
+    else vm_wait<0>();
     // every wave's pieces landed; every wave is done reading the buffers row it+3 overwrites
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    lds_barrier();
     if (it + SW_NB - 1 < n_mine) issue(it + SW_NB - 1, in, ih);
     next(in, ih);
     const char* srow = s2d + (int)(((long)n * a.Hs + h + wave) & (SW_NS - 1)) * SW_SLOT;
@@ -173,17 +148,14 @@ __global__ void __launch_bounds__(256, 1) stem_wgrad_kernel(SwArgs a) {
 #pragma unroll
       for (int b = 0; b < 4; ++b) x[b] = s2d_frag(srow, b, ks, lane);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) y[j] = dy_frag(img, 16 * j, ks, lane);
+      for (int j = 0; j < 4; ++j) y[j] = frag_kouter_async<64, true>(img, 16 * j, ks, lane);
     };
     load(0, fx[0], fy[0]);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      // (the asm reads' results exist only after that wait: tie the k-step's fragments to it)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) asm volatile("" : "+v"(fx[ks & 1][b]));
-#pragma unroll
-      for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(fy[ks & 1][j]));
+      lds_wait();
+      tie(fx[ks & 1]);
+      tie(fy[ks & 1]);
       if (ks < 3) load(ks + 1, fx[(ks + 1) & 1], fy[(ks + 1) & 1]);
       // D[c][k]: src0 = s2d^T (rows c), src1 = dY (columns k)
 #pragma unroll
@@ -223,13 +195,6 @@ struct SwfArgs {
   const float* coef;    // [3][64]
   int P2, Q2;
 };
-
-typedef int v4i_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void lds_write16(char* p, uint4 v) {
-  const uint32_t ad = (uint32_t)(uintptr_t)LDS_PTR(char, p);
-  const v4i_t x = __builtin_bit_cast(v4i_t, v);
-  asm volatile("ds_write_b128 %0, %1" ::"v"(ad), "v"(x) : "memory");
-}
 
 struct SwWin {
   uint2 a;
@@ -301,8 +266,8 @@ __device__ __forceinline__ void swf_transform(const SwfArgs& f, int h, int u, co
   const uint4 v1 = make_uint4(pack2bf(o1[0], o1[1]), pack2bf(o1[2], o1[3]), pack2bf(o1[4], o1[5]),
                               pack2bf(o1[6], o1[7]));
   const int p0 = 2 * j, p1 = 2 * j + 1;
-  lds_write16(img + p0 * 128 + ((cc ^ (kouter_swz<64>(p0) << 1)) << 4), v0);
-  lds_write16(img + p1 * 128 + ((cc ^ (kouter_swz<64>(p1) << 1)) << 4), v1);
+  lds_store16(img + p0 * 128 + ((cc ^ (kouter_swz<64>(p0) << 1)) << 4), __builtin_bit_cast(v4i, v0));
+  lds_store16(img + p1 * 128 + ((cc ^ (kouter_swz<64>(p1) << 1)) << 4), __builtin_bit_cast(v4i, v1));
 }
 
 // 10 s2d row slots (9 in use at most: rows it, it+1 and it+2's four at an image boundary) keep the block at 79.5 KB
@@ -345,7 +310,7 @@ __global__ void __launch_bounds__(256, 2) stem_wgrad_fused_kernel(SwfArgs f) {
     }
   }
   const int sx = sw_px(t >> 1);
-  const uint32_t soff = sx < a.Ws ? (uint32_t)(sx * 32 + (t & 1) * 16) : 0x80000000u;
+  const uint32_t soff = sx < a.Ws ? (uint32_t)(sx * 32 + (t & 1) * 16) : OOB_OFF;
   // s2d rows of output row `it` (4 pieces per thread always: unneeded / past-the-end ones go to the junk area)
   auto issue_s2d = [&](int it, int n, int h) {
     const int first = (it == 0 || h == 0) ? 0 : 3;
@@ -354,11 +319,9 @@ __global__ void __launch_bounds__(256, 2) stem_wgrad_fused_kernel(SwfArgs f) {
     for (int j = 0; j < 4; ++j) {
       const int L = n * a.Hs + h + j;
       const bool need = live && j >= first;
-      const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-          (void*)(a.X + (long)(need ? L : 0) * a.Ws * 16), (short)0, a.Ws * 32, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rx = buf_rsrc(a.X + (long)(need ? L : 0) * a.Ws * 16, a.Ws * 32);
       char* dst = need ? s2d + (L % SWF_NS) * SW_SLOT : junk;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          rx, (__attribute__((address_space(3))) void*)(dst + wave * 1024), 16, need ? soff : 0x80000000u, 0, 0, 0);
+      dma16(rx, dst + wave * 1024, need ? soff : OOB_OFF);
     }
   };
   int n = (int)(r0 / a.P), h = (int)(r0 % a.P);  // row it
@@ -390,7 +353,7 @@ __global__ void __launch_bounds__(256, 2) stem_wgrad_fused_kernel(SwfArgs f) {
 
   for (int it = 0; it < n_mine; ++it) {
     // everything up to row it's registers landed (after them only row it+1's s2d pieces: 4)
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    vm_wait<4>();
     char* img = dyi + (it & 1) * SW_DY;
     if (has0) swf_transform(f, h, u0, ra, ka, kb, kc, img);
     if (has1) swf_transform(f, h, u1, rb, ka, kb, kc, img);
@@ -403,7 +366,7 @@ __global__ void __launch_bounds__(256, 2) stem_wgrad_fused_kernel(SwfArgs f) {
     next(ln, lh);
     // this row's dY image and s2d rows are complete for every wave; every wave is done with the image row it+1
     // overwrites and with the s2d slots row it+2 takes
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    lds_barrier();
     issue_s2d(it + 2, in, ih);
     next(in, ih);
     const char* srow = s2d + ((n * a.Hs + h + wave) % SWF_NS) * SW_SLOT;
@@ -414,12 +377,10 @@ __global__ void __launch_bounds__(256, 2) stem_wgrad_fused_kernel(SwfArgs f) {
 #pragma unroll
       for (int b = 0; b < 4; ++b) fx[b] = s2d_frag(srow, b, ks, lane);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) fy[j] = dy_frag(img, 16 * j, ks, lane);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int b = 0; b < 4; ++b) asm volatile("" : "+v"(fx[b]));
-#pragma unroll
-      for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(fy[j]));
+      for (int j = 0; j < 4; ++j) fy[j] = frag_kouter_async<64, true>(img, 16 * j, ks, lane);
+      lds_wait();
+      tie(fx);
+      tie(fy);
 #pragma unroll
       for (int b = 0; b < 4; ++b)
 #pragma unroll
@@ -428,7 +389,7 @@ __global__ void __launch_bounds__(256, 2) stem_wgrad_fused_kernel(SwfArgs f) {
     }
     next(n, h);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  vm_wait<0>();
 
   float* slab = a.ws + (long)blockIdx.x * SW_OUT;
 #pragma unroll
@@ -461,7 +422,8 @@ DTF_API int dtf_stem_wgrad(const void* X, const void* dY, float* dW, int N, int 
   a.rpb = (int)((a.rows + grid - 1) / grid);
   grid = (int)((a.rows + a.rpb - 1) / a.rpb);
   hipStream_t st = (hipStream_t)stream;
-  static const int nb = getenv("DTF_STEM_NB") ? atoi(getenv("DTF_STEM_NB")) : 4;  // ring depth (A/B sweep)
+  static RouteSwitch ring{"DTF_STEM_NB", 4, true};  // ring depth (A/B sweep)
+  const int nb = ring.get();
   if (nb == 3) hipLaunchKernelGGL(stem_wgrad_kernel<3>, dim3(grid), dim3(256), 0, st, a);
   else if (nb == 5) hipLaunchKernelGGL(stem_wgrad_kernel<5>, dim3(grid), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(stem_wgrad_kernel<4>, dim3(grid), dim3(256), 0, st, a);

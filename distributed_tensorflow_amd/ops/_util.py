@@ -532,7 +532,7 @@ LAUNCH_COUNTERS = ("w4_256", "w4_128", "gemm256", "gemm_tile", "gemm_dact", "bet
 
 
 def launch_counts():
-    """Host-side launch counters of the GEMM dispatch (csrc/kernels/common.h LaunchCounter): which kernel a GEMM
+    """Host-side launch counters of the GEMM dispatch (csrc/kernels/routes.h LaunchCounter): which kernel a GEMM
     reached. Take two snapshots and subtract."""
     import ctypes
     n = len(LAUNCH_COUNTERS)

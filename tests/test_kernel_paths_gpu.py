@@ -6,7 +6,7 @@
 * It also fails on the aten sort / indexed-row ops (sort, index_select, index_add, scatter_add, gather, ...) with a
   CUDA operand: the embedding gradient's sort and the masked-LM gather run csrc/kernels/sort.hip,
   checked over a BERT-base-shaped MLM step too.
-* The GEMM dispatch's host-side launch counters (csrc/kernels/common.h LaunchCounter) show which kernel a call reached,
+* The GEMM dispatch's host-side launch counters (csrc/kernels/routes.h LaunchCounter) show which kernel a call reached,
   so these steps are also pinned to the hand-written 4-wave GEMM (gemm_w4.hip) where the dense layers should land.
 Dispatch modes are thread-local state that autograd propagates to its backward threads, so the backward is covered.
 """
