@@ -63,20 +63,24 @@ class MultiHeadSelfAttention(KL.Layer):
         self.qkv = _Proj(3 * hidden, fp8=fp8)
         self.out = _Proj(hidden, fp8=fp8)
 
-    def call(self, x, mask=None, training=None, link=None, cache=None, layer=None):
+    def call(self, x, mask=None, training=None, link=None, cache=None, layer=None, append=False):
         if cache is not None:
-            return self._call_cached(x, cache, layer)
+            return self._call_cached(x, cache, layer, append)
         o = attn_ops.attention_packed(self.qkv(x, link=link), self.heads, causal=self.causal, mask=mask,
                                       dropout=self.dropout, training=training)
         return self.out(o)
 
-    def _call_cached(self, x, cache, layer):
+    def _call_cached(self, x, cache, layer, append=False):
         """Inference with a KV cache (ops.decode.KVCache): S > 1 is the prefill of an empty cache (the causal
-        attention kernel, plus a copy of K and V into the cache), S == 1 a decode step (append, then attend)."""
+        attention kernel, plus a copy of K and V into the cache), S == 1 a decode step (append, then attend);
+        append=True with S > 1 appends the chunk to a filled cache (store at lens + s, then attend_chunk)."""
         qkv = self.qkv(x, cache=cache)
         if x.shape[1] == 1:
             cache.store(layer, qkv)
             o = cache.attend(layer, qkv)
+        elif append:
+            cache.store(layer, qkv)
+            o = cache.attend_chunk(layer, qkv)
         else:
             o = attn_ops.attention_packed(qkv, self.heads, causal=True, dropout=0.0, training=False)
             cache.store(layer, qkv)
@@ -173,9 +177,9 @@ class GPT2Block(KL.Layer):
         self.dropout = dropout
         object.__setattr__(self, "out_into_ln", False)  # set by GPT2: the output's first reader is a LayerNorm
 
-    def call(self, x, training=None, cache=None, layer=None):
+    def call(self, x, training=None, cache=None, layer=None, append=False):
         if cache is not None:  # inference with a KV cache: no dropout, no gradient links
-            x = ops.add(x, self.att(self.ln1(x), training=False, cache=cache, layer=layer))
+            x = ops.add(x, self.att(self.ln1(x), training=False, cache=cache, layer=layer, append=append))
             return ops.add(x, self.proj(self.fc(self.ln2(x), cache=cache), cache=cache))
         # the residual gradient of each half-block's input joins its LayerNorm's backward (ResidualGradLink)
         l1, l2 = (ResidualGradLink(), ResidualGradLink()) if (LN_LINK and training and x.is_cuda
@@ -215,27 +219,105 @@ class GPT2(Model):
         self.dropout = dropout
         self.built = True
 
-    def call(self, ids, training=None, cache=None):
+    def call(self, ids, training=None, cache=None, append=False):
         if cache is not None:
-            return self._lm_head(self._hidden_cached(ids, cache), decode=ids.shape[1] == 1)
+            return self._lm_head(self._hidden_cached(ids, cache, append), decode=ids.shape[1] == 1)
         x = ops.dropout(ops.embedding(ids, self.wte, self.wpe), self.dropout, training=bool(training))
         for b in self.blocks:
             x = b(x, training=training)
         return ops.dense(self.ln_f(x), self.wte, self.pad_bias)  # tied LM head, logits over vocab_p
 
     # ---- inference with a KV cache (ops.decode)
-    def _hidden_cached(self, ids, cache):
+    def _hidden_cached(self, ids, cache, append=False):
         """Final hidden states [B, S, hidden] of an inference forward that fills `cache`: S > 1 prefills an empty
-        cache, S == 1 is a decode step at positions cache.lens (the caller advances lens once per token)."""
-        if ids.shape[1] == 1:
-            x = ops.embedding(ids, self.wte, self.wpe, position_ids=cache.lens)
-        elif not cache.empty:
-            raise NotImplementedError("chunked prefill into a non-empty KV cache")
-        else:
+        cache, S == 1 is a decode step at positions cache.lens, and append=True with S > 1 on a cache that is not empty
+        appends the chunk at positions cache.lens + s (the caller advances lens afterwards in every case).
+        With append=True the positions are clamped on the device to the position table, for S == 1 too: the pad token
+        of a ragged row that is already full sits at position ctx (its output is never picked, its K/V are dropped or
+        rewritten). The default one-token step embeds at cache.lens as it is."""
+        S = ids.shape[1]
+        chunk = False
+        top = self.cfg["ctx"] - 1
+        if S == 1:
+            x = ops.embedding(ids, self.wte, self.wpe, position_ids=cache.lens.clamp(0, top) if append else cache.lens)
+        elif cache.empty:
             x = ops.embedding(ids, self.wte, self.wpe)
+        elif not append:
+            raise NotImplementedError("chunked prefill into a non-empty KV cache needs append=True (or GPT2.extend)")
+        else:
+            self._refuse_gpu_chunk(ids, cache, S, False)   # before anything is stored
+            chunk = True
+            # pad positions of ragged rows may run past the position table: clamped on the device, never read back
+            pos = cache.lens[:, None] + torch.arange(S, device=ids.device)[None, :]
+            x = ops.embedding(ids, self.wte, self.wpe, position_ids=pos.clamp_(0, top))
         for i, b in enumerate(self.blocks):
-            x = b(x, training=False, cache=cache, layer=i)
+            x = b(x, training=False, cache=cache, layer=i, append=chunk)
         return self.ln_f(x)
+
+    @staticmethod
+    def _refuse_gpu_chunk(ids, cache, n, more):
+        """The one GPU refusal of the append route (KVCache.attend_chunk has no GPU kernel for S > 1; remove with it):
+        a piece of n > 1 tokens that would land behind a filled cache, now or (more: further pieces follow) once the
+        first piece has filled it. Raised before the cache is touched."""
+        if ids.is_cuda and n > 1 and (more or not cache.empty):
+            raise NotImplementedError(f"appending {n} > 1 tokens at once to a filled KV cache has no GPU kernel yet; "
+                                      "feed one token at a time (extend(chunk=1), generate(prefill_chunk=1))")
+
+    @staticmethod
+    def _fits(ids, cache):
+        """ids [B, S] and the cache agree in batch and device ('cuda' names the current device)."""
+        def key(d):
+            d = torch.device(d)
+            return d.type, (torch.cuda.current_device() if d.index is None else d.index) if d.type == "cuda" else 0
+        return ids.shape[0] == cache.batch and key(ids.device) == key(cache.device)
+
+    def extend(self, ids, cache, new_lens=None, chunk=None):
+        """Feed ids [B, S] (right-padded, new_lens [B] valid tokens per row, default S) into `cache` behind what it
+        holds, in pieces of at most `chunk` tokens (default: all at once) -> logits [B, vocab_p] after each row's last
+        valid token. cache.lens advances per row by the valid count only; no device value is read on the host.
+        A row with new_lens[b] == 0 takes nothing, and its returned logits are undefined (those of a pad token).
+
+        Room is the caller's to guarantee (checking it would be a host read of lens; `generate` does it once per
+        call): every row needs lens[b] + new_lens[b] <= min(cache.capacity, ctx). Past the capacity `store` drops
+        K/V silently and past ctx positions are clamped to the last table row, so an overfull row returns logits that
+        mean nothing, without an error.
+
+        Invariant (the one the ragged prefill of `generate` relies on): a position at or past lens is always rewritten
+        before anything attends to it. A piece stores K/V of its pad tokens past a short row's valid end, but lens
+        stops at that end, so the next piece or decode step of the row overwrites them first.
+
+        On the GPU a piece of more than one token can only fill an empty cache (the prefill kernel); behind a filled
+        cache pieces are single tokens (chunk=1: the decode step's kernels), anything else raises NotImplementedError
+        before the cache is touched: the multi-token append has no GPU kernel yet and no eager fallback."""
+        ids = ids.long()
+        B, S = ids.shape
+        dev = ids.device
+        if not self._fits(ids, cache):
+            raise ValueError(f"extend: ids {tuple(ids.shape)} on {dev} against a cache of batch {cache.batch} on "
+                             f"{cache.device}")
+        if S < 1:
+            raise ValueError("extend needs at least one token")
+        step = S if chunk is None else int(chunk)
+        if step < 1:
+            raise ValueError(f"extend: chunk {chunk}")
+        self._refuse_gpu_chunk(ids, cache, min(step, S), S > step)
+        with torch.no_grad():
+            if new_lens is None:
+                nl = torch.full((B,), S, dtype=torch.int64, device=dev)
+            else:
+                nl = torch.as_tensor(new_lens).to(dev).long()
+            base = torch.arange(B, device=dev)
+            last = None
+            for lo in range(0, S, step):
+                n = min(step, S - lo)
+                piece = ids[:, lo:lo + n].contiguous()
+                h = self._hidden_cached(piece, cache, append=True)
+                valid = (nl - lo).clamp(0, n)                  # valid tokens of each row in this piece
+                rows = (valid - 1).clamp(min=0) + base * n     # (a row with none keeps its earlier pick)
+                got = ops.gather_rows(h.reshape(B * n, -1), rows)
+                last = got if last is None else torch.where((valid > 0)[:, None], got, last)
+                cache.advance(valid)
+            return self._lm_head(last.reshape(B, 1, -1), decode=True)[:, 0]
 
     def _lm_head(self, h, decode=False):
         if decode:
@@ -259,8 +341,14 @@ class GPT2(Model):
         return torch.multinomial(torch.softmax(lg, -1), 1, generator=gen)[:, 0]
 
     def generate(self, ids, max_new_tokens, *, prompt_lens=None, temperature=0.0, top_k=None, seed=None,
-                 eos_token_id=None, pad_token_id=None, graph=True):
+                 eos_token_id=None, pad_token_id=None, graph=True, cache=None, prefill_chunk=None):
         """Continue `ids` [B, S0] by max_new_tokens tokens with a KV cache -> int64 [B, S0 + max_new_tokens].
+
+        cache: a KVCache to continue (``last_generation["cache"]`` of an earlier call, or one filled through
+        `extend`): ids / prompt_lens are then the new tokens only and follow what the cache holds; cached + new +
+        generated tokens must fit min(cache.capacity, ctx) (checked with one host read of cache.lens before the token
+        loop). prefill_chunk=N feeds the prompt through `extend` in pieces of N tokens (on the GPU a filled cache takes
+        single-token pieces only: see `extend`). With both left at None the call runs as described below.
 
         One prefill forward over the prompt, then one single-token step per new token (decode attention over the
         cache, weight-streaming projections); on a GPU with graph=True the step is captured into a hipGraph and
@@ -278,7 +366,16 @@ class GPT2(Model):
             raise ValueError(f"prompt ({S0}) + max_new_tokens ({n_new}) exceeds the context length {ctx}")
         if S0 < 1 or n_new < 0:
             raise ValueError("generate needs a non-empty prompt and max_new_tokens >= 0")
-        if n_new == 0:
+        if cache is not None:
+            if not self._fits(ids, cache):
+                raise ValueError(f"generate: ids {tuple(ids.shape)} on {dev} against a cache of batch {cache.batch} on "
+                                 f"{cache.device}")
+            # the one host read of a call with a cache: before the token loop, outside any capture
+            held, room = int(cache.lens.max()), min(cache.capacity, ctx)
+            if held + S0 + n_new > room:
+                raise ValueError(f"cached tokens ({held}) + new tokens ({S0}) + max_new_tokens ({n_new}) exceed "
+                                 f"min(cache capacity {cache.capacity}, context length {ctx})")
+        if n_new == 0 and cache is None:
             return ids.clone()
         pad = pad_token_id if pad_token_id is not None else (eos_token_id if eos_token_id is not None else 0)
         gen = None
@@ -286,16 +383,21 @@ class GPT2(Model):
             gen = torch.Generator(device=dev)
             gen.manual_seed(0 if seed is None else int(seed))
         with torch.no_grad():
-            cache = self.new_cache(B, S0 + n_new, dev)
             if prompt_lens is None:
                 plens = torch.full((B,), S0, dtype=torch.int64, device=dev)
             else:
                 plens = torch.as_tensor(prompt_lens).to(dev).long()
-            h = self._hidden_cached(ids, cache)  # prefill: K/V of all S0 positions; a pad position is rewritten
-            cache.set_lens(plens)                # by the decode step that reaches it before anything attends to it
-            rows = plens - 1 + torch.arange(B, device=dev) * S0
-            last = ops.gather_rows(h.reshape(B * S0, -1), rows)  # each row's own last prompt position
-            logits = self._lm_head(last.reshape(B, 1, -1), decode=True)[:, 0]
+            if cache is None and prefill_chunk is None:
+                cache = self.new_cache(B, S0 + n_new, dev)
+                h = self._hidden_cached(ids, cache)  # prefill: K/V of all S0 positions; a pad position is rewritten
+                cache.set_lens(plens)                # by the decode step that reaches it before anything attends to it
+                rows = plens - 1 + torch.arange(B, device=dev) * S0
+                last = ops.gather_rows(h.reshape(B * S0, -1), rows)  # each row's own last prompt position
+                logits = self._lm_head(last.reshape(B, 1, -1), decode=True)[:, 0]
+            else:
+                if cache is None:
+                    cache = self.new_cache(B, S0 + n_new, dev)
+                logits = self.extend(ids, cache, plens, prefill_chunk)  # behind what the cache holds, in pieces
 
             def step(tok):
                 lg = self._lm_head(self._hidden_cached(tok, cache), decode=True)

@@ -6,6 +6,8 @@ A decode step computes one token per sequence: its attention reads the keys and 
 tensor shared by the layers (valid positions per batch row; also the position ids of the step's embedding) and the
 split-KV scratch. Per layer a step calls ``store`` (append at ``lens``), then ``attend``; the caller ``advance``s
 ``lens`` once per token. Nothing reads a device value on the host, so a step is hipGraph-capturable.
+``attend_chunk`` is the same rule for S queries per row (query s sees positions 0 .. min(lens + s, capacity-1)): the
+CPU reference of appending a multi-token chunk to a filled cache; on the GPU only S == 1 (``attend``) has a kernel.
 
 ``dense_skinny`` is an explicit route: ``ops.dense`` / ``ops.gemm`` dispatch as before and never reach it.
 CPU tensors take the explicit f32 torch path.
@@ -95,6 +97,29 @@ class KVCache:
         p = torch.softmax(s.masked_fill(dead[:, None, None, :], float("-inf")), -1)
         o = torch.matmul(p, self.v[layer])                                     # [B, H, 1, D]
         return o.permute(0, 2, 1, 3).reshape(B, 1, HD).to(qkv.dtype)
+
+    def attend_chunk(self, layer, qkv, scale=None):
+        """S query rows per (b, h) from qkv [B, S, 3*H*D] over a filled cache (store first: query s's own key is
+        position lens[b] + s): query s attends positions 0 .. min(lens[b] + s, capacity-1), `attend`'s rule per query
+        -> [B, S, H*D]. S == 1 is `attend` itself (same kernel, same bits). S > 1 has the explicit f32 path for CPU
+        tensors only: there is no GPU kernel for it yet, and a missing kernel is an error, never an eager fallback —
+        on the GPU feed one token at a time (GPT2.extend(chunk=1), generate(prefill_chunk=1))."""
+        self._check(layer, qkv)
+        B, S, _ = qkv.shape
+        if S == 1:
+            return self.attend(layer, qkv, scale)
+        HD = self.heads * self.head_dim
+        scale = float(scale) if scale is not None else 1.0 / math.sqrt(self.head_dim)
+        if on_gpu(qkv):
+            raise NotImplementedError(f"attend_chunk: no GPU kernel for a chunk of {S} > 1 queries over a filled KV "
+                                      "cache; feed one token at a time (chunk=1 / prefill_chunk=1)")
+        q = qkv[:, :, :HD].float().reshape(B, S, self.heads, self.head_dim).transpose(1, 2)   # [B, H, S, D]
+        lim = (self.lens.clamp(min=0)[:, None] + torch.arange(S)[None, :]).clamp(max=self.capacity - 1)  # [B, S]
+        s = torch.matmul(q, self.k[layer].transpose(-1, -2)) * scale                           # [B, H, S, Smax]
+        dead = torch.arange(self.capacity)[None, None, :] > lim[:, :, None]                    # [B, S, Smax]
+        p = torch.softmax(s.masked_fill(dead[:, None], float("-inf")), -1)
+        o = torch.matmul(p, self.v[layer])                                                     # [B, H, S, D]
+        return o.transpose(1, 2).reshape(B, S, HD).to(qkv.dtype)
 
     def advance(self, n=1):
         self.lens.add_(n)
