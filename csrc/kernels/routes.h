@@ -37,6 +37,7 @@ enum LaunchCounter : int {
   LC_GEMM256_FP8 = 9, // gemm256.hip with fp8 operands
   LC_ATTN_DECODE = 10,  // attn_decode.hip, split-KV single-token attention (partials + merge count as one)
   LC_DENSE_SKINNY = 11, // attn_decode.hip, M <= 16 weight-streaming dense
+  LC_SAMPLE = 12,       // sample.hip, the fused token sampler
   LC_COUNT = 16
 };
 DTF_API long* dtf_launch_counters();  // gemm.hip

@@ -341,7 +341,8 @@ class GPT2(Model):
         return torch.multinomial(torch.softmax(lg, -1), 1, generator=gen)[:, 0]
 
     def generate(self, ids, max_new_tokens, *, prompt_lens=None, temperature=0.0, top_k=None, seed=None,
-                 eos_token_id=None, pad_token_id=None, graph=True, cache=None, prefill_chunk=None):
+                 eos_token_id=None, pad_token_id=None, graph=True, cache=None, prefill_chunk=None, top_p=None,
+                 repetition_penalty=None, sampler=None):
         """Continue `ids` [B, S0] by max_new_tokens tokens with a KV cache -> int64 [B, S0 + max_new_tokens].
 
         cache: a KVCache to continue (``last_generation["cache"]`` of an earlier call, or one filled through
@@ -356,7 +357,22 @@ class GPT2(Model):
         its tail is pad_token_id. temperature 0 is greedy; otherwise temperature / top-k sampling from a
         torch.Generator seeded with `seed`. After eos_token_id a row emits pad_token_id (decided on the device: the
         loop reads no device value and always runs max_new_tokens steps). The cache and the logits after the last
-        token are kept in ``last_generation`` (to inspect or continue)."""
+        token are kept in ``last_generation`` (to inspect or continue).
+
+        sampler="fused" picks every token with ``ops.sample_logits`` (one kernel launch: penalty, temperature, top-k,
+        top-p, a counter-hash draw keyed by seed, row and position, and the eos / pad / output bookkeeping). It is also
+        the route whenever top_p (nucleus) or repetition_penalty is given; sampler="torch" with either raises. The
+        output tokens, each row's position and its done flag live on the device, and with graph=True the sampler launch
+        and the model step are one captured step: a new token is one replay with no eager device op in between. The
+        same arguments give the same tokens on the CPU reference path of the sampler as on the GPU kernel for equal
+        logits, eagerly and replayed, and for a row alone or among others at the same row index. The penalty applies
+        to the tokens this call was given and produced (with cache=, not to what the cache already held). With all
+        three left at None the torch.Generator route above runs unchanged."""
+        if sampler not in (None, "torch", "fused"):
+            raise ValueError(f"generate: sampler {sampler!r} (None, 'torch' or 'fused')")
+        if sampler == "torch" and (top_p is not None or repetition_penalty is not None):
+            raise ValueError("generate: top_p and repetition_penalty need the fused sampler")
+        fused = sampler == "fused" or (sampler is None and (top_p is not None or repetition_penalty is not None))
         ids = ids.long()
         B, S0 = ids.shape
         dev = ids.device
@@ -379,7 +395,7 @@ class GPT2(Model):
             return ids.clone()
         pad = pad_token_id if pad_token_id is not None else (eos_token_id if eos_token_id is not None else 0)
         gen = None
-        if temperature:
+        if temperature and not fused:
             gen = torch.Generator(device=dev)
             gen.manual_seed(0 if seed is None else int(seed))
         with torch.no_grad():
@@ -404,21 +420,38 @@ class GPT2(Model):
                 cache.advance(1)
                 return lg
 
-            captured = None
-            if graph and dev.type == "cuda":
-                from ..graphs import CapturedStep
-                captured = CapturedStep(step, split=False)  # one stream only: a graph without parallel branches
             col = torch.arange(S0, device=dev)[None, :]
             out = torch.full((B, S0 + n_new), int(pad), dtype=torch.int64, device=dev)
             out[:, :S0] = torch.where(col < plens[:, None], ids, out[:, :S0])
             done = torch.zeros(B, dtype=torch.bool, device=dev)
-            for t in range(n_new):
-                tok = self._pick(logits, temperature, top_k, gen)
-                if eos_token_id is not None:
-                    tok = torch.where(done, torch.full_like(tok, int(pad)), tok)
-                    done = done | (tok == int(eos_token_id))
-                out.scatter_(1, (plens + t)[:, None], tok[:, None])
-                logits = (captured or step)(tok[:, None].contiguous())[:, 0]
+            if fused:
+                # the step reads `logits` and rewrites it in place, so a replay takes no argument and copies nothing in
+                logits = logits.contiguous().clone()
+                pos = plens.clone()
+
+                def fused_step(_):
+                    tok = ops.sample_logits(logits, n=self.vocab, temperature=temperature, top_k=top_k, top_p=top_p,
+                                            repetition_penalty=repetition_penalty, seed=seed, out=out, pos=pos,
+                                            done=done, eos=eos_token_id, pad=int(pad))
+                    logits.copy_(step(tok[:, None])[:, 0])
+                    return logits
+
+            captured = None
+            if graph and dev.type == "cuda":
+                from ..graphs import CapturedStep
+                # one stream only: a graph without parallel branches
+                captured = CapturedStep(fused_step if fused else step, split=False)
+            if fused:
+                for t in range(n_new):
+                    (captured or fused_step)(())
+            else:
+                for t in range(n_new):
+                    tok = self._pick(logits, temperature, top_k, gen)
+                    if eos_token_id is not None:
+                        tok = torch.where(done, torch.full_like(tok, int(pad)), tok)
+                        done = done | (tok == int(eos_token_id))
+                    out.scatter_(1, (plens + t)[:, None], tok[:, None])
+                    logits = (captured or step)(tok[:, None].contiguous())[:, 0]
             logits = logits.clone()
         object.__setattr__(self, "last_generation", {"cache": cache, "logits": logits, "step": captured})
         return out

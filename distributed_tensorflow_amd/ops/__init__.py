@@ -8,3 +8,4 @@ from .nn import (max_pool2d, global_avg_pool, relu, gelu, dropout, add, add_drop
 from .optim import optim_apply  # noqa: F401
 from .mha import attention, attention_packed  # noqa: F401
 from .decode import KVCache, dense_skinny  # noqa: F401
+from .sample import sample_logits, sample_reference  # noqa: F401

@@ -10,6 +10,10 @@ min..max spread over the rounds is reported; times are host clocks around work t
     6.29 TB/s copy bandwidth. The cache rotates over 16 layers (537 MB) so the reads come from HBM, not from a cache.
  3. ops.dense_skinny against ops.dense on the five GPT-2-medium projection shapes at M = 1, 8, 16, rotating over
     enough weight copies (>= 512 MB where they fit) that each call streams its weights from HBM as a decode step does.
+ 4. (--sections 4) token choice: generate(graph=True, temperature=0.8, top_k=40) at B in {1, 8} with the torch route
+    (aten topk / softmax / multinomial between two replays) against sampler="fused" (ops.sample_logits captured with the
+    step), ms/token from the difference of a long and a short call of the same arm; and ops.sample_logits alone at
+    n = 50257.
 """
 import argparse
 import os
@@ -183,12 +187,71 @@ def section_dense(dev, rounds):
         + (", ".join(f"{k}->{n} at M={m}" for k, n, m in slower) if slower else "none"))
 
 
+def section_sampler(dev, rounds):
+    say("== 4. token choice in generate(graph=True, temperature=0.8, top_k=40), GPT-2-medium: torch route vs "
+        "sampler=\"fused\"")
+    short, long_ = 16, 112
+    ratios = {}
+    with context.device(dev), torch.no_grad():
+        model = gpt2_medium(dropout=0.0)
+        for B in (1, 8):
+            torch.manual_seed(B)
+            ids = torch.randint(0, model.vocab, (B, 64), device=dev)
+
+            def per_token(sampler):
+                def go():
+                    ts = []
+                    for n in (short, long_):
+                        torch.cuda.synchronize()
+                        t = time.perf_counter()
+                        model.generate(ids, n, temperature=0.8, top_k=40, seed=1, graph=True, sampler=sampler)
+                        torch.cuda.synchronize()
+                        ts.append(time.perf_counter() - t)
+                    return (ts[1] - ts[0]) / (long_ - short)
+                return go
+
+            arms = {"torch": per_token("torch"), "fused": per_token("fused")}
+            for fn in arms.values():
+                fn()
+            res = {k: [] for k in arms}
+            for _ in range(rounds):
+                for k, fn in arms.items():
+                    res[k].append(fn())
+            ratios[B] = statistics.median(res["fused"]) / statistics.median(res["torch"])
+            say(f"B={B} prompt 64, tokens {short}..{long_} of a call (prefill and capture cancel in the difference):")
+            say(f"    torch route  {fmt(res['torch'])} /token")
+            say(f"    fused route  {fmt(res['fused'])} /token  -> fused / torch = {ratios[B]:.3f}")
+        del model
+    torch.cuda.empty_cache()
+    say("ops.sample_logits alone, n = 50257 (ld 50304, bf16 logits ~ N(0, 4^2)), 16 calls inside one replayed graph:")
+    with torch.no_grad():
+        for B in (1, 8):
+            x = (torch.randn(B, 50304, device=dev) * 4).to(torch.bfloat16)
+            out = torch.randint(0, 50257, (B, 256), device=dev)
+            done = torch.zeros(B, dtype=torch.bool, device=dev)
+            for name, kw in (("T=0.8 k=40", dict(temperature=0.8, top_k=40)),
+                             ("T=0.9 p=0.9", dict(temperature=0.9, top_p=0.9)),
+                             ("T=1.3 k=50 p=0.8 r=1.2", dict(temperature=1.3, top_k=50, top_p=0.8,
+                                                            repetition_penalty=1.2)),
+                             ("greedy", dict(temperature=0.0))):
+                pos = torch.full((B,), 128, dtype=torch.int64, device=dev)
+
+                def sweep():
+                    for _ in range(16):
+                        ops.sample_logits(x, n=50257, seed=3, out=out, pos=pos, done=done, **kw)
+
+                ts = [t / 16 for t in rounds_of({"s": graph_of(sweep)}, rounds, 10)["s"]]
+                say(f"    B={B} {name:24s} {fmt(ts, 1e6, 'us')} per call")
+    return ratios
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                                   "profiles", "generate_decode.txt"))
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--sections", default="1,2,3")
+    ap.add_argument("--append", action="store_true", help="append to --out instead of replacing it")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_generate needs a GPU: nothing here can be measured on a CPU")
@@ -201,8 +264,10 @@ def main():
         section_dense(dev, a.rounds)
     if "1" in sec:
         section_generate(dev, a.rounds)
+    if "4" in sec:
+        section_sampler(dev, a.rounds)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
+    with open(a.out, "a" if a.append else "w") as f:
         f.write("\n".join(LINES) + "\n")
 
 
