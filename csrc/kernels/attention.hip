@@ -18,6 +18,7 @@
 // one key and gathers the bits across its lane quad. Masking work is skipped on tiles that are entirely
 // below the causal diagonal.
 #include "common.h"
+#include "routes.h"
 
 namespace {
 
@@ -386,6 +387,137 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_kernel(AttnArgs a, int nblk) 
     if (blk < 0) break;
     if (pass) __syncthreads();  // the previous block's last tile is no longer read
     attn_fwd_body<QT, DROP>(a, blk, sk, sv, smask);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ append
+// S queries per batch row behind a filled KV cache (attn_decode.hip's layout: K and V [B, H, Smax, 64] of one layer,
+// already holding this chunk's K/V; lens[B] int64 on the device): the forward's loop with QT = 1 and the key count and
+// causal offset of each batch row read from lens on the device, so a launch does not depend on the lengths (identical
+// eagerly and under hipGraph capture). Row b: len = clamp(lens[b], 0, Smax), Sk = min(len + S, Smax); query s sees key
+// k iff k < Sk and k <= s + len. No dropout, no key mask, no LSE. The cache is uninitialised memory at and past Sk:
+// those rows are zero-filled on load (K and V alike) and their scores are assigned -inf, so nothing there reaches the
+// arithmetic; rows below Sk were written earlier or by this call's dtf_kv_store.
+struct AppendArgs {
+  const bf16_t* qkv;  // [B, S, 3*H*64], queries are the first third
+  const bf16_t* kc;
+  const bf16_t* vc;
+  const long* lens;
+  bf16_t* out;        // [B, S, H*64]
+  int B, S, H, Smax;
+  float scale;
+};
+
+// block: 4 waves x 16 queries; grid (cdiv(S, 64), B*H). No heavy/light pairing: every block walks the cached prefix.
+// Every wave takes part in all tile loads and barriers of its block (also one whose 16 queries lie at or past S).
+__global__ void __launch_bounds__(256, 2) attn_append_kernel(AppendArgs a) {
+  __shared__ __attribute__((aligned(16))) char sk[64 * 128];
+  __shared__ __attribute__((aligned(16))) char sv[64 * 128];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, G = lane >> 4, i = lane & 15;
+  const int bh = attn_by(), b = bh / a.H, h = bh % a.H, blk = attn_bx();
+  long len = a.lens[b];
+  len = len < 0 ? 0 : (len > a.Smax ? a.Smax : len);
+  const int off = (int)len;                    // query s sits at position off + s
+  const int Sk = min(off + a.S, a.Smax);       // >= 1
+  const int q0 = blk * 64 + w * 16, qi = q0 + i;
+  const long HD3 = 3l * a.H * HD;
+  const bf16_t* Q = a.qkv + (long)b * a.S * HD3 + h * HD;
+  const bf16_t* K = a.kc + (long)bh * a.Smax * HD;
+  const bf16_t* V = a.vc + (long)bh * a.Smax * HD;
+  const float c = a.scale * LOG2E;
+
+  v8bf qf[2];
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) qf[kk] = frag_global(Q + (long)qi * HD3 + 32 * kk + 8 * G, qi < a.S);
+  v4f o[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) o[dt] = v4f{0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, l = 0.f;
+  const int kend = min(Sk, off + min(a.S, blk * 64 + 64));  // >= 1: the block's last valid query's last key, + 1
+  const int ntiles = (kend + 63) / 64;
+  TileRegs tk, tv;
+  tile_load(tk, K, HD, 0, Sk);
+  tile_load(tv, V, HD, 0, Sk);
+  for (int t = 0; t < ntiles; ++t) {
+    __syncthreads();
+    tile_store(tk, sk);
+    tile_store(tv, sv);
+    __syncthreads();
+    const int k0 = t * 64;
+    if (t + 1 < ntiles) {
+      tile_load(tk, K, HD, k0 + 64, Sk);
+      tile_load(tv, V, HD, k0 + 64, Sk);
+    }
+    v4f s[4];
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+      v4f acc = {0.f, 0.f, 0.f, 0.f};
+      acc = mfma(frag_row(sk, 16 * kt, 0, lane), qf[0], acc);
+      s[kt] = mfma(frag_row(sk, 16 * kt, 1, lane), qf[1], acc);
+    }
+    // wave-uniform: some key of the tile is hidden from the wave's first query, or lies at or past Sk
+    const bool edge = k0 + 63 > q0 + off || k0 + 64 > Sk;
+    float mnew;
+    if (!edge) {
+      float mx = s[0][0];
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[kt][r]);
+      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      mnew = fmaxf(m, mx * c);  // (c > 0) finite: every key of the tile is valid
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s[kt][r] = fmaf(s[kt][r], c, -mnew);
+    } else {
+      const int klim = min(qi + off, Sk - 1);  // the lane's query sees keys 0 .. klim
+      float mx = -INFINITY;
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          // assigned, never added: the score of a zero-filled row is 0, of a hidden valid row finite
+          const float x = k0 + 16 * kt + 4 * G + r > klim ? -INFINITY : s[kt][r] * c;
+          s[kt][r] = x;
+          mx = fmaxf(mx, x);
+        }
+      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      mnew = fmaxf(m, mx);  // finite from tile 0 on: every query sees key 0
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s[kt][r] -= mnew;
+    }
+    const float alpha = ex2(m - mnew);
+    m = mnew;
+    float ls = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        s[kt][r] = ex2(s[kt][r]);
+        ls += s[kt][r];
+      }
+    l = l * alpha + ls;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) o[dt] *= alpha;
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      const v8bf pf = pack_slots(s[2 * kk], s[2 * kk + 1]);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) o[dt] = mfma(frag_tr(sv, 32 * kk, 16 * dt, lane), pf, o[dt]);
+    }
+  }
+  float L = l + __shfl_xor(l, 16, 64);
+  L += __shfl_xor(L, 32, 64);
+  if (qi < a.S) {
+    bf16_t* O = a.out + ((long)b * a.S + qi) * a.H * HD + h * HD;
+    const float inv = 1.f / L;  // L > 0: key 0 is visible to every query
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) store4(O + 16 * dt + 4 * G, o[dt], inv);
   }
 }
 
@@ -893,6 +1025,25 @@ DTF_API int dtf_attn_fwd(const void* q, const void* k, const void* v, const long
   dim3 grid(pair_grid(causal, nqb), (unsigned)(B * H));
   if (a.thr < 65536u) hipLaunchKernelGGL((attn_fwd_kernel<2, true>), grid, dim3(256), 0, (hipStream_t)stream, a, nqb);
   else hipLaunchKernelGGL((attn_fwd_kernel<2, false>), grid, dim3(256), 0, (hipStream_t)stream, a, nqb);
+  return (int)hipGetLastError();
+}
+
+// Multi-token append attention over a KV cache (attn_append_kernel): qkv [B, S, 3*H*64] bf16 (queries: its first third,
+// read in place), k_cache / v_cache [B, H, Smax, 64] bf16 of one layer with this chunk already stored (dtf_kv_store
+// first, on the same stream), lens int64 [B] on the device (read on the device only), out [B, S, H*64] bf16. One launch,
+// no scratch, no atomics: bitwise repeatable. -1: a null pointer, a bf16 pointer off 16 bytes (lens: off 8), a size
+// below 1, B*H above the grid's 65535.
+DTF_API int dtf_attn_append(const void* qkv, const void* k_cache, const void* v_cache, const long* lens, void* out,
+                            int B, int S, int H, int Smax, float scale, void* stream) {
+  if (!qkv || !k_cache || !v_cache || !lens || !out || B < 1 || S < 1 || H < 1 || Smax < 1) return -1;
+  if (!aligned16(qkv) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(out) || ((uintptr_t)lens & 7))
+    return -1;
+  if ((long)B * H > 65535) return -1;
+  AppendArgs a{(const bf16_t*)qkv, (const bf16_t*)k_cache, (const bf16_t*)v_cache, lens, (bf16_t*)out, B, S, H, Smax,
+               scale};
+  hipLaunchKernelGGL(attn_append_kernel, dim3((unsigned)((S + 63) / 64), (unsigned)(B * H)), dim3(256), 0,
+                     (hipStream_t)stream, a);
+  count_launch(LC_ATTN_APPEND);
   return (int)hipGetLastError();
 }
 

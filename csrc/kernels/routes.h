@@ -38,6 +38,7 @@ enum LaunchCounter : int {
   LC_ATTN_DECODE = 10,  // attn_decode.hip, split-KV single-token attention (partials + merge count as one)
   LC_DENSE_SKINNY = 11, // attn_decode.hip, M <= 16 weight-streaming dense
   LC_SAMPLE = 12,       // sample.hip, the fused token sampler
+  LC_ATTN_APPEND = 13,  // attention.hip, multi-token append attention over a KV cache
   LC_COUNT = 16
 };
 DTF_API long* dtf_launch_counters();  // gemm.hip

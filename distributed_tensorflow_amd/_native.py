@@ -138,6 +138,8 @@ _KERNEL_SIGS = {
     "dtf_attn_decode": [P, P, P, P, P, P, I, I, I, F, P],
     "dtf_attn_decode_chunk": [],
     "dtf_dense_skinny": [P, P, P, P, I, I, I, I, P],
+    # multi-token append attention over the cache (attention.hip): qkv, k, v, lens, out, B, S, H, Smax, scale, stream
+    "dtf_attn_append": [P, P, P, P, P, I, I, I, I, F, P],
     # fused token sampler (sample.hip): logits, f32, ld, B, n, 1/T, greedy, top_k, P, r, 1/r, seed, uniform, table, out,
     # width, pos, done, eos, pad, tok_out, stream
     "dtf_sample_logits": [P, I, L, I, I, F, I, I, I, F, F, U, P, P, P, L, P, P, L, L, P, P],

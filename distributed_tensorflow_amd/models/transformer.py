@@ -256,12 +256,14 @@ class GPT2(Model):
 
     @staticmethod
     def _refuse_gpu_chunk(ids, cache, n, more):
-        """The one GPU refusal of the append route (KVCache.attend_chunk has no GPU kernel for S > 1; remove with it):
-        a piece of n > 1 tokens that would land behind a filled cache, now or (more: further pieces follow) once the
-        first piece has filled it. Raised before the cache is touched."""
-        if ids.is_cuda and n > 1 and (more or not cache.empty):
-            raise NotImplementedError(f"appending {n} > 1 tokens at once to a filled KV cache has no GPU kernel yet; "
-                                      "feed one token at a time (extend(chunk=1), generate(prefill_chunk=1))")
+        """The one GPU refusal of the append route (KVCache.attend_chunk runs S > 1 on the GPU only for a cache built
+        with chunked=True; remove with that opt-in): a piece of n > 1 tokens that would land behind a filled default
+        cache, now or (more: further pieces follow) once the first piece has filled it. Raised before the cache is
+        touched."""
+        if ids.is_cuda and n > 1 and (more or not cache.empty) and not getattr(cache, "chunked", False):
+            raise NotImplementedError(f"appending {n} > 1 tokens at once to a filled KV cache needs a cache built with "
+                                      "chunked=True (new_cache(..., chunked=True)); feed this one a token at a time "
+                                      "(extend(chunk=1), generate(prefill_chunk=1))")
 
     @staticmethod
     def _fits(ids, cache):
@@ -286,9 +288,11 @@ class GPT2(Model):
         before anything attends to it. A piece stores K/V of its pad tokens past a short row's valid end, but lens
         stops at that end, so the next piece or decode step of the row overwrites them first.
 
-        On the GPU a piece of more than one token can only fill an empty cache (the prefill kernel); behind a filled
-        cache pieces are single tokens (chunk=1: the decode step's kernels), anything else raises NotImplementedError
-        before the cache is touched: the multi-token append has no GPU kernel yet and no eager fallback."""
+        On the GPU the first piece into an empty cache runs the prefill kernel. Behind a filled cache a piece of more
+        than one token runs the multi-token append kernel (ops.decode.KVCache.attend_chunk) when the cache was built
+        with chunked=True (new_cache(..., chunked=True)); on a default cache pieces are single tokens (chunk=1: the
+        decode step's kernels) and anything else raises NotImplementedError before the cache is touched, with no eager
+        fallback."""
         ids = ids.long()
         B, S = ids.shape
         dev = ids.device
@@ -324,9 +328,12 @@ class GPT2(Model):
             return decode_ops.step_dense(h, self.wte, self.pad_bias)
         return ops.dense(h, self.wte, self.pad_bias)
 
-    def new_cache(self, batch, capacity, device):
+    def new_cache(self, batch, capacity, device, chunked=False):
+        """A KV cache for this model. chunked=True: on the GPU multi-token pieces behind a filled cache run the append
+        kernel (extend(chunk=N), generate(cache=, prefill_chunk=N)); a default cache refuses them."""
         c = self.cfg
-        return decode_ops.KVCache(c["layers"], batch, c["heads"], capacity, device, head_dim=c["hidden"] // c["heads"])
+        return decode_ops.KVCache(c["layers"], batch, c["heads"], capacity, device, head_dim=c["hidden"] // c["heads"],
+                                  chunked=chunked)
 
     def _pick(self, logits, temperature, top_k, gen):
         """Next token per row from logits [B, vocab_p]: argmax, or temperature / top-k sampling, over the real
@@ -348,8 +355,9 @@ class GPT2(Model):
         cache: a KVCache to continue (``last_generation["cache"]`` of an earlier call, or one filled through
         `extend`): ids / prompt_lens are then the new tokens only and follow what the cache holds; cached + new +
         generated tokens must fit min(cache.capacity, ctx) (checked with one host read of cache.lens before the token
-        loop). prefill_chunk=N feeds the prompt through `extend` in pieces of N tokens (on the GPU a filled cache takes
-        single-token pieces only: see `extend`). With both left at None the call runs as described below.
+        loop). prefill_chunk=N feeds the prompt through `extend` in pieces of N tokens (on the GPU a cache passed in
+        takes pieces of more than one token only if it was built with chunked=True: see `extend`; the cache this call
+        creates itself for prefill_chunk is). With both left at None the call runs as described below.
 
         One prefill forward over the prompt, then one single-token step per new token (decode attention over the
         cache, weight-streaming projections); on a GPU with graph=True the step is captured into a hipGraph and
@@ -411,8 +419,8 @@ class GPT2(Model):
                 last = ops.gather_rows(h.reshape(B * S0, -1), rows)  # each row's own last prompt position
                 logits = self._lm_head(last.reshape(B, 1, -1), decode=True)[:, 0]
             else:
-                if cache is None:
-                    cache = self.new_cache(B, S0 + n_new, dev)
+                if cache is None:  # (prefill_chunk given: the pieces after the first land behind a filled cache)
+                    cache = self.new_cache(B, S0 + n_new, dev, chunked=True)
                 logits = self.extend(ids, cache, plens, prefill_chunk)  # behind what the cache holds, in pieces
 
             def step(tok):

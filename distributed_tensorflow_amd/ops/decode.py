@@ -7,7 +7,9 @@ tensor shared by the layers (valid positions per batch row; also the position id
 split-KV scratch. Per layer a step calls ``store`` (append at ``lens``), then ``attend``; the caller ``advance``s
 ``lens`` once per token. Nothing reads a device value on the host, so a step is hipGraph-capturable.
 ``attend_chunk`` is the same rule for S queries per row (query s sees positions 0 .. min(lens + s, capacity-1)): the
-CPU reference of appending a multi-token chunk to a filled cache; on the GPU only S == 1 (``attend``) has a kernel.
+CPU reference of appending a multi-token chunk to a filled cache. On the GPU S == 1 is ``attend``; S > 1 runs the
+multi-token append kernel (``dtf_attn_append``, csrc/kernels/attention.hip) on a cache built with ``chunked=True`` and
+raises on a default cache (the route is opt-in per cache for now).
 
 ``dense_skinny`` is an explicit route: ``ops.dense`` / ``ops.gemm`` dispatch as before and never reach it.
 CPU tensors take the explicit f32 torch path.
@@ -31,7 +33,7 @@ def decode_chunk():
 
 
 class KVCache:
-    def __init__(self, layers, batch, heads, capacity, device, head_dim=HEAD_DIM):
+    def __init__(self, layers, batch, heads, capacity, device, head_dim=HEAD_DIM, chunked=False):
         self.device = torch.device(device)
         gpu = self.device.type == "cuda"
         if gpu and head_dim != HEAD_DIM:
@@ -44,6 +46,8 @@ class KVCache:
         self.v = torch.empty(shape, dtype=BF16, device=self.device) if gpu else torch.zeros(shape, dtype=F32)
         self.lens = torch.zeros(self.batch, dtype=torch.int64, device=self.device)
         self.empty = True  # host-side: nothing stored since the last reset
+        # GPU: attend_chunk with S > 1 runs the append kernel (False: it raises); the CPU path takes any S either way
+        self.chunked = bool(chunked)
         self.scratch = None
         if gpu:
             self.nchunks = -(-self.capacity // decode_chunk())
@@ -101,9 +105,10 @@ class KVCache:
     def attend_chunk(self, layer, qkv, scale=None):
         """S query rows per (b, h) from qkv [B, S, 3*H*D] over a filled cache (store first: query s's own key is
         position lens[b] + s): query s attends positions 0 .. min(lens[b] + s, capacity-1), `attend`'s rule per query
-        -> [B, S, H*D]. S == 1 is `attend` itself (same kernel, same bits). S > 1 has the explicit f32 path for CPU
-        tensors only: there is no GPU kernel for it yet, and a missing kernel is an error, never an eager fallback —
-        on the GPU feed one token at a time (GPT2.extend(chunk=1), generate(prefill_chunk=1))."""
+        -> [B, S, H*D]. S == 1 is `attend` itself (same kernel, same bits). S > 1: the explicit f32 path for CPU tensors;
+        on the GPU one launch of the append kernel when the cache was built with chunked=True (lens is read on the
+        device only: capturable), and NotImplementedError on a default cache, never an eager fallback — feed such a
+        cache one token at a time (GPT2.extend(chunk=1), generate(prefill_chunk=1))."""
         self._check(layer, qkv)
         B, S, _ = qkv.shape
         if S == 1:
@@ -111,8 +116,16 @@ class KVCache:
         HD = self.heads * self.head_dim
         scale = float(scale) if scale is not None else 1.0 / math.sqrt(self.head_dim)
         if on_gpu(qkv):
-            raise NotImplementedError(f"attend_chunk: no GPU kernel for a chunk of {S} > 1 queries over a filled KV "
-                                      "cache; feed one token at a time (chunk=1 / prefill_chunk=1)")
+            if not self.chunked:
+                raise NotImplementedError(f"attend_chunk: no GPU kernel for a chunk of {S} > 1 queries over a filled "
+                                          "KV cache built without chunked=True; feed one token at a time (chunk=1 / "
+                                          "prefill_chunk=1)")
+            q = qkv if qkv.dtype == BF16 else qkv.to(BF16)
+            q = q.contiguous()
+            out = torch.empty(B, S, HD, dtype=BF16, device=qkv.device)
+            call("dtf_attn_append", ptr(q), ptr(self.k[layer]), ptr(self.v[layer]), ptr(self.lens), ptr(out), B, S,
+                 self.heads, self.capacity, scale, stream(qkv.device))
+            return out
         q = qkv[:, :, :HD].float().reshape(B, S, self.heads, self.head_dim).transpose(1, 2)   # [B, H, S, D]
         lim = (self.lens.clamp(min=0)[:, None] + torch.arange(S)[None, :]).clamp(max=self.capacity - 1)  # [B, S]
         s = torch.matmul(q, self.k[layer].transpose(-1, -2)) * scale                           # [B, H, S, Smax]

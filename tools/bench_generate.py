@@ -14,6 +14,9 @@ min..max spread over the rounds is reported; times are host clocks around work t
     (aten topk / softmax / multinomial between two replays) against sampler="fused" (ops.sample_logits captured with the
     step), ms/token from the difference of a long and a short call of the same arm; and ops.sample_logits alone at
     n = 50257.
+ 5. (--sections 5) continuing a filled cache: N in {16, 64, 256} new tokens behind L in {1, 256, 768} cached ones at
+    B in {1, 8}: token by token (extend(chunk=1), and the captured one-token step replayed N times) against one chunked
+    extend on a chunked=True cache; and dtf_attn_append alone with the K/V bytes it must read over its time.
 """
 import argparse
 import os
@@ -245,6 +248,93 @@ def section_sampler(dev, rounds):
     return ratios
 
 
+def section_append(dev, rounds):
+    say("== 5. N new tokens behind a cache holding L (GPT-2-medium, capacity 1024): token by token vs one chunked call")
+    say("token by token: extend(chunk=1) on a default cache (eager, the route without the append kernel) and the "
+        "captured one-token step replayed N times; chunked: extend() of all N on a chunked=True cache, eager")
+    ratios = {}
+    with context.device(dev), torch.no_grad():
+        model = gpt2_medium(dropout=0.0)
+        for B in (1, 8):
+            caches = {}
+            for chunked in (False, True):
+                c = model.new_cache(B, 1024, dev, chunked=chunked)
+                c.k.normal_()
+                c.v.normal_()
+                c.empty = False  # "filled": only lens says how far
+                caches[chunked] = c
+            tok = torch.randint(0, model.vocab, (B, 1), device=dev)
+
+            def step(t):
+                lg = model(t, training=False, cache=caches[False])
+                caches[False].advance(1)
+                return lg
+
+            caches[False].lens.fill_(1)
+            cap = CapturedStep(step, split=False)
+            for _ in range(4):
+                cap(tok)
+            assert cap.captured
+            for L in (1, 256, 768):
+                for N in (16, 64, 256):
+                    if L + N > 1024:
+                        continue
+                    torch.manual_seed(B * 100000 + L * 1000 + N)
+                    ids = torch.randint(0, model.vocab, (B, N), device=dev)
+
+                    def one_by_one():
+                        caches[False].lens.fill_(L)
+                        model.extend(ids, caches[False], chunk=1)
+
+                    def replayed():
+                        caches[False].lens.fill_(L)
+                        for _ in range(N):
+                            cap(tok)
+
+                    def chunk_call():
+                        caches[True].lens.fill_(L)
+                        model.extend(ids, caches[True])
+
+                    r = rounds_of({"one": one_by_one, "replay": replayed, "chunk": chunk_call}, rounds, 1)
+                    med = {k: statistics.median(v) for k, v in r.items()}
+                    ratios[(B, L, N)] = (med["one"] / med["chunk"], med["replay"] / med["chunk"])
+                    say(f"B={B} L={L:3d} N={N:3d}: extend(chunk=1) {fmt(r['one'])}   captured step x N "
+                        f"{fmt(r['replay'])}   one chunked call {fmt(r['chunk'])}   -> x{ratios[(B, L, N)][0]:.1f} / "
+                        f"x{ratios[(B, L, N)][1]:.1f}")
+            del cap, caches
+        layers, H = model.cfg["layers"], model.cfg["heads"]
+        del model
+    torch.cuda.empty_cache()
+    say(f"dtf_attn_append alone (H = {H}, capacity 1024, rotating over {layers} layers inside one replayed graph): K+V "
+        "bytes it must read (each once) over its time; MFMA work 4 * 64 * visible (query, key) pairs")
+    with torch.no_grad():
+        for B in (1, 8):
+            cache = ops.KVCache(layers, B, H, 1024, dev, chunked=True)
+            cache.k.normal_()
+            cache.v.normal_()
+            for L in (1, 256, 768):
+                for N in (16, 64, 256):
+                    if L + N > 1024:
+                        continue
+                    cache.lens.fill_(L)
+                    qkv = torch.randn(B, N, 3 * H * 64, device=dev).to(torch.bfloat16)
+
+                    def sweep():
+                        for l in range(layers):
+                            cache.attend_chunk(l, qkv)
+
+                    ts = [t / layers for t in rounds_of({"a": graph_of(sweep)}, rounds, 20)["a"]]
+                    t = statistics.median(ts)
+                    nbytes = 2 * B * H * (L + N) * 64 * 2
+                    flops = 4 * 64 * B * H * (N * L + N * (N + 1) // 2)
+                    say(f"    B={B} L={L:3d} N={N:3d} ({-(-N // 64) * B * H:4d} blocks): {fmt(ts, 1e6, 'us')}; K+V "
+                        f"{nbytes / 1e6:6.2f} MB -> {nbytes / t / 1e12:.3f} TB/s ({100 * nbytes / t / COPY_BW:.0f}% of "
+                        f"copy bw), {flops / t / 1e12:.2f} TFLOP/s")
+            del cache
+    torch.cuda.empty_cache()
+    return ratios
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
@@ -266,6 +356,8 @@ def main():
         section_generate(dev, a.rounds)
     if "4" in sec:
         section_sampler(dev, a.rounds)
+    if "5" in sec:
+        section_append(dev, a.rounds)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "a" if a.append else "w") as f:
         f.write("\n".join(LINES) + "\n")
