@@ -423,7 +423,7 @@ __device__ __forceinline__ void ce_online(float v, float& m, float& s) {
     s = s * __expf(m - v) + 1.f;
     m = v;
   } else {
-    s += __expf(v - m);
+    s += v == -INFINITY ? 0.f : __expf(v - m);  // a -inf logit adds nothing (exp(-inf - m) is NaN while m is -inf)
   }
 }
 
@@ -461,7 +461,8 @@ __global__ void __launch_bounds__(256) softmax_ce_fwd_kernel(const void* __restr
     if (lab >= 0) {
       const float xl = in_f32 ? reinterpret_cast<const float*>(logits)[r * V + lab]
                               : bf2f(reinterpret_cast<const bf16_t*>(logits)[r * V + lab]);
-      l = (1.f - smooth) * (lse - xl) + smooth * (lse - SX / V);
+      l = (1.f - smooth) * (lse - xl);
+      if (smooth != 0.f) l += smooth * (lse - SX / V);  // SX is -inf for a row with -inf logits: 0 * inf is NaN
     }
     loss[r] = l;
     lse_out[r] = lse;

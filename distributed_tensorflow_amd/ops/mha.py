@@ -16,7 +16,7 @@ import torch
 
 from ._util import BF16, F32, call, on_gpu, ptr, rng_counter, stream
 from .linalg import bmm
-from .nn import softmax
+from .nn import masked_row_softmax, softmax
 
 _seed_counter = [0]
 
@@ -161,7 +161,7 @@ def attention(q, k, v, causal=False, mask=None, scale=None, dropout=0.0, trainin
         s = s.masked_fill(~m, float("-inf"))
     if mask is not None:
         s = s + mask.reshape(B, 1, 1, Sk).float()
-    p = torch.softmax(s, -1)
+    p = masked_row_softmax(s)  # rows with no visible key: 0, as the kernels
     if rate:
         p = torch.nn.functional.dropout(p, rate)
     return torch.matmul(p, v.float()).to(q.dtype)
@@ -209,7 +209,7 @@ def reference_attention(q, k, v, causal=False, mask=None, scale=None, keep_mask=
         s = s.masked_fill(~m, float("-inf"))
     if mask is not None:
         s = s + mask.reshape(B, 1, 1, Sk).float()
-    p = torch.softmax(s, -1)
+    p = masked_row_softmax(s)  # rows with no visible key: 0, as the kernels
     if keep_mask is not None:
         p = p * keep_mask / keep
     return torch.matmul(p, v.float())

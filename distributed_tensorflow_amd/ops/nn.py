@@ -436,7 +436,9 @@ def sparse_softmax_cross_entropy(logits, labels, label_smoothing=0.0):
     """Per-example loss of tf.nn.sparse_softmax_cross_entropy_with_logits (fused fwd+grad kernel)."""
     if on_gpu(logits):
         return _SoftmaxCEFn.apply(logits, labels, float(label_smoothing))
-    return torch.nn.functional.cross_entropy(logits.float().reshape(-1, logits.shape[-1]), labels.reshape(-1).long(),
+    lab = labels.reshape(-1).long()
+    lab = torch.where(lab < 0, torch.full_like(lab, -100), lab)  # as the kernel: any negative label is an ignored row
+    return torch.nn.functional.cross_entropy(logits.float().reshape(-1, logits.shape[-1]), lab,
                                              reduction="none", label_smoothing=label_smoothing,
                                              ignore_index=-100).reshape(labels.shape)
 
@@ -476,4 +478,11 @@ def softmax(x, scale=1.0, causal=False, add_mask=None):
         z = z.masked_fill(~m, float("-inf"))
     if add_mask is not None:
         z = z + add_mask.reshape(*z.shape[:-2], 1, z.shape[-1])
-    return torch.softmax(z, dim=-1).to(x.dtype)
+    return masked_row_softmax(z).to(x.dtype)
+
+
+def masked_row_softmax(z):
+    """softmax over the last axis of scores masked with -inf; a row with no visible key is 0 (what the kernels write
+    for it), not the NaN of exp(-inf + inf), and passes a zero gradient."""
+    dead = (z == float("-inf")).all(-1, keepdim=True)
+    return torch.softmax(z.masked_fill(dead, 0.0), dim=-1).masked_fill(dead, 0.0)
