@@ -6,6 +6,8 @@
 // conv epilogue (gemm.hip `stats`), so the standalone path here is:
 //   bn_stats (only when no conv produced them) -> bn_finalize (per channel,
 //   also updates running stats TF-style) -> bn_apply (scale/shift [+res] [+relu]).
+//   The standalone statistics are sums of x - x[row 0] and its apply pass is (x - mean) * scale + beta, so a channel
+//   whose mean is large against its spread (or constant) loses nothing to cancellation.
 // Backward: bn_bwd_reduce (sum dz, sum dz*xhat with the ReLU mask applied
 //   on the fly) -> bn_bwd_finalize -> bn_bwd_apply (dx, optional dz for the
 //   residual branch). All passes are 16-B vectorized and grid-stride; reductions
@@ -57,6 +59,9 @@ __device__ __forceinline__ void block_col_partials(float (&s)[8], float (&q)[8],
 }
 
 // Standalone BN statistics: partial [gridDim.x][2C] rows (no atomics; summed by bn_finalize).
+// The sums are taken of x - pivot, pivot = row 0 of x (per channel): sum and sum of squares of the shifted values give
+// var = E[(x-p)^2] - E[x-p]^2 without the cancellation of E[x^2] - mean^2 when |mean| >> std (a constant channel has
+// variance exactly 0). bn_finalize_kernel adds the pivot back to the mean (dtf_bn_finalize_pivot).
 __global__ void __launch_bounds__(256) bn_stats_kernel(const bf16_t* __restrict__ x, long M, int C,
                                                        float* __restrict__ part) {
   __shared__ float red[4096];
@@ -67,11 +72,13 @@ __global__ void __launch_bounds__(256) bn_stats_kernel(const bf16_t* __restrict_
     const int cc = cc0 + t % g.TPR;
     float s[8] = {0}, q[8] = {0};
     if (t < g.TPR * g.RPB && cc < g.cols8) {
+      float pv[8];
+      load8(x + cc * 8, pv);
       for (long r = (long)blockIdx.x * g.RPB + rsub; r < M; r += (long)gridDim.x * g.RPB) {
         float f[8];
         load8(x + r * C + cc * 8, f);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { s[j] += f[j]; q[j] += f[j] * f[j]; }
+        for (int j = 0; j < 8; ++j) { const float d = f[j] - pv[j]; s[j] += d; q[j] += d * d; }
       }
     }
     block_col_partials(s, q, cc0, g.TPR, g.RPB, C, part + (long)blockIdx.x * 2 * C, red);
@@ -111,15 +118,18 @@ __global__ void __launch_bounds__(FIN_NT) bn_finalize_kernel(const float* __rest
                                                           float* running_var, long M, int C, float momentum,
                                                           float eps, float* __restrict__ scale,
                                                           float* __restrict__ shift, float* __restrict__ mean_out,
-                                                          float* __restrict__ invstd_out) {
+                                                          float* __restrict__ invstd_out,
+                                                          const bf16_t* __restrict__ pivot) {
   __shared__ float red[2][FIN_G][64];
   const int cl = threadIdx.x & 63, grp = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + cl;
   float a, b;
   fin_rows(part, T, rs, C, c, c < C, red, a, b);
   if (grp != 0 || c >= C) return;
-  float mean = a / (float)M;
-  float var = fmaxf(b / (float)M - mean * mean, 0.f);
+  // pivot (optional): the partial sums are of x - pivot[c] (bn_stats_kernel); without it d is the mean itself
+  const float d = a / (float)M;
+  float mean = pivot ? bf2f(pivot[c]) + d : d;
+  float var = fmaxf(b / (float)M - d * d, 0.f);
   float inv = rsqrtf(var + eps);
   float gm = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
   scale[c] = gm * inv;
@@ -215,22 +225,33 @@ __device__ __forceinline__ void bn_apply_row(const bf16_t* __restrict__ x, const
 
 // rscale/rshift (optional): the residual is itself a BatchNorm input (a projection shortcut's conv output) whose
 // affine normalisation is applied here, so the shortcut's BN output is never materialised.
-template <int NU = EU>  // rows per trip (all loads of a trip issued before the first use)
+// CEN: y = (x - center) * scale + shift with shift = beta and center = the batch mean. x - mean is exact where it
+// matters (x near the mean), so a channel whose |mean| * scale is large (variance ~ 0) keeps y = beta, where the folded
+// x * scale + (beta - mean * scale) loses 2^-24 |mean * scale|.
+template <int NU = EU, bool CEN = false>  // rows per trip (all loads of a trip issued before the first use)
 __global__ void __launch_bounds__(256) bn_apply_kernel(const bf16_t* __restrict__ x, const float* __restrict__ scale,
                                                        const float* __restrict__ shift,
                                                        const bf16_t* __restrict__ res, bf16_t* __restrict__ y,
                                                        long M, int C, int relu, uint8_t* __restrict__ mbits,
                                                        const float* __restrict__ rscale,
-                                                       const float* __restrict__ rshift, int rev) {
+                                                       const float* __restrict__ rshift, int rev,
+                                                       const float* __restrict__ center) {
   const ColGeo g = colgeo(C);
   const int t = threadIdx.x;
   if (t >= g.TPR * g.RPB) return;
   const int rsub = t / g.TPR;
   const long rstep = (long)gridDim.x * g.RPB;
   for (int cc = t % g.TPR; cc < g.cols8; cc += g.TPR) {
-    float sc[8], sh[8], rsc[8], rsh[8];
+    float sc[8], sh[8], rsc[8], rsh[8], mu[8];
     load_coef8(scale + cc * 8, sc);
     load_coef8(shift + cc * 8, sh);
+    if constexpr (CEN) load_coef8(center + cc * 8, mu);
+    auto cen = [&](float* f) {
+      if constexpr (CEN) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] -= mu[j];
+      }
+    };
     if (rscale) {
       load_coef8(rscale + cc * 8, rsc);
       load_coef8(rshift + cc * 8, rsh);
@@ -253,6 +274,7 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const bf16_t* __restrict_
 #pragma unroll
       for (int u = 0; u < NU; ++u) {
         if (res) raff(rv[u]);
+        cen(f[u]);
         bn_apply_row(x, res, y, mbits, (rev ? M - 1 - (r + u * rstep) : r + u * rstep) * g.cols8 + cc, f[u], rv[u],
                      sc, sh, relu);
       }
@@ -265,6 +287,7 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const bf16_t* __restrict_
         load8(res + i8 * 8, rv);
         raff(rv);
       }
+      cen(f);
       bn_apply_row(x, res, y, mbits, i8, f, rv, sc, sh, relu);
     }
   }
@@ -948,7 +971,8 @@ int ew_grid(long M, int C, int nu = EU) {
 
 }  // namespace
 
-// Statistics of x: writes G partial rows into `part` (capacity >= 1024*2*C floats), returns G via *rows.
+// Statistics of x - x[row 0] (per channel): writes G partial rows into `part` (capacity >= 1024*2*C floats), returns
+// G via *rows. Finalize them with dtf_bn_finalize_pivot(part, G, x, ...).
 DTF_API int dtf_bn_stats(const void* x, long M, int C, float* part, int* rows, void* stream) {
   if (C & 7) return -1;
   int G = red_grid(M, C);
@@ -957,15 +981,23 @@ DTF_API int dtf_bn_stats(const void* x, long M, int C, float* part, int* rows, v
   return (int)hipGetLastError();
 }
 
-DTF_API int dtf_bn_finalize(float* part, int T, const float* gamma, const float* beta, float* running_mean,
-                            float* running_var, long M, int C, float momentum, float eps, float* scale,
-                            float* shift, float* mean_out, float* invstd_out, void* stream) {
+// pivot (optional, bf16 [C]): the partial rows are sums of x - pivot (dtf_bn_stats: row 0 of x)
+DTF_API int dtf_bn_finalize_pivot(float* part, int T, const void* pivot, const float* gamma, const float* beta,
+                                  float* running_mean, float* running_var, long M, int C, float momentum, float eps,
+                                  float* scale, float* shift, float* mean_out, float* invstd_out, void* stream) {
   long rs = 2L * C;
   T = dtf_group_rows_once(part, rs, T, 2L * C, bn_group_target(), &rs, stream);  // <= target leader rows, one launch
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, 64)), dim3(FIN_NT), 0, (hipStream_t)stream, part, T, rs, gamma,
-                     beta,
-                     running_mean, running_var, M, C, momentum, eps, scale, shift, mean_out, invstd_out);
+                     beta, running_mean, running_var, M, C, momentum, eps, scale, shift, mean_out, invstd_out,
+                     (const bf16_t*)pivot);
   return (int)hipGetLastError();
+}
+
+DTF_API int dtf_bn_finalize(float* part, int T, const float* gamma, const float* beta, float* running_mean,
+                            float* running_var, long M, int C, float momentum, float eps, float* scale,
+                            float* shift, float* mean_out, float* invstd_out, void* stream) {
+  return dtf_bn_finalize_pivot(part, T, nullptr, gamma, beta, running_mean, running_var, M, C, momentum, eps, scale,
+                               shift, mean_out, invstd_out, stream);
 }
 
 DTF_API int dtf_set_ew_variant(int v) {
@@ -993,7 +1025,19 @@ DTF_API int dtf_bn_apply(const void* x, const float* scale, const float* shift, 
   hipLaunchKernelGGL((nu == 2 ? bn_apply_kernel<2> : nu == 8 ? bn_apply_kernel<8> : bn_apply_kernel<4>),
                      dim3(ew_grid(M, C, nu == 2 || nu == 8 ? nu : 4)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)x, scale, shift, (const bf16_t*)res, (bf16_t*)y, M, C, relu,
-                     relu ? (uint8_t*)mbits : nullptr, res ? rscale : nullptr, res ? rshift : nullptr, ew_reverse());
+                     relu ? (uint8_t*)mbits : nullptr, res ? rscale : nullptr, res ? rshift : nullptr, ew_reverse(),
+                     nullptr);
+  return (int)hipGetLastError();
+}
+
+// y = [relu]((x - center) * scale + beta [+ res]): the apply pass of a standalone training BatchNorm (center = the
+// batch mean of dtf_bn_finalize_pivot); see bn_apply_kernel CEN. mbits as in dtf_bn_apply.
+DTF_API int dtf_bn_apply_centered(const void* x, const float* scale, const float* center, const float* beta,
+                                  const void* res, void* y, long M, int C, int relu, void* mbits, void* stream) {
+  if ((C & 7) || !center || !beta) return -1;
+  hipLaunchKernelGGL((bn_apply_kernel<2, true>), dim3(ew_grid(M, C, 2)), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)x, scale, beta, (const bf16_t*)res, (bf16_t*)y, M, C, relu,
+                     relu ? (uint8_t*)mbits : nullptr, nullptr, nullptr, ew_reverse(), center);
   return (int)hipGetLastError();
 }
 

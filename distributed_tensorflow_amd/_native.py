@@ -49,6 +49,8 @@ _KERNEL_SIGS = {
     "dtf_stem_wgrad_fused": [P, P, P, P, P, P, I, I, I, I, P, L, P],
     "dtf_bn_stats": [P, L, I, P, P, P],
     "dtf_bn_finalize": [P, I, P, P, P, P, L, I, F, F, P, P, P, P, P],
+    "dtf_bn_finalize_pivot": [P, I, P, P, P, P, P, L, I, F, F, P, P, P, P, P],
+    "dtf_bn_apply_centered": [P, P, P, P, P, P, L, I, I, P, P],
     "dtf_bn_infer_coeff": [P, P, P, P, I, F, P, P, P],
     "dtf_bn_apply": [P, P, P, P, P, L, I, I, P, P, P, P],
     "dtf_bn_bwd": [P, P, P, P, P, P, P, L, I, P, P, P, P, I, P, P, P, P, P, P],

@@ -41,8 +41,9 @@ class _BNFn(torch.autograd.Function):
             part = torch.empty(1024 * 2 * C, dtype=F32, device=x.device)
             rows = IntOut()
             call("dtf_bn_stats", ptr(x), M, C, ptr(part), rows.addr, stream())
-            call("dtf_bn_finalize", ptr(part), rows.value, ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar), M, C,
-                 float(momentum), float(eps), ptr(scale), ptr(shift), ptr(mean), ptr(invstd), stream())
+            # the statistics are sums of x - x[row 0] (no E[x^2] - mean^2 cancellation); x is the pivot row
+            call("dtf_bn_finalize_pivot", ptr(part), rows.value, ptr(x), ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar),
+                 M, C, float(momentum), float(eps), ptr(scale), ptr(shift), ptr(mean), ptr(invstd), stream())
         else:
             call("dtf_bn_infer_coeff", ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar), C, float(eps), ptr(scale),
                  ptr(shift), stream())
@@ -50,8 +51,14 @@ class _BNFn(torch.autograd.Function):
         if res is not None:
             res = res.to(BF16).contiguous()
         mbits = torch.empty(M * C // 8, dtype=torch.uint8, device=x.device) if relu else None
-        call("dtf_bn_apply", ptr(x), ptr(scale), ptr(shift), ptr(res), ptr(out), M, C, int(relu), ptr(mbits),
-             None, None, stream())
+        if training:
+            # (x - mean) * scale + beta: exact where x is near the mean, whatever |mean| * scale is
+            bt = beta if beta is not None else torch.zeros(C, dtype=F32, device=x.device)
+            call("dtf_bn_apply_centered", ptr(x), ptr(scale), ptr(mean), ptr(bt), ptr(res), ptr(out), M, C,
+                 int(relu), ptr(mbits), stream())
+        else:
+            call("dtf_bn_apply", ptr(x), ptr(scale), ptr(shift), ptr(res), ptr(out), M, C, int(relu), ptr(mbits),
+                 None, None, stream())
         ctx.save_for_backward(x, gamma, mbits, mean, invstd)
         ctx.relu = relu
         ctx.has_res = res is not None
@@ -86,6 +93,9 @@ def batch_norm(x, gamma, beta, rmean, rvar, training=True, momentum=0.99, eps=1e
         y = y + residual.float()
     y = torch.relu(y) if relu else y
     return y.to(x.dtype) if x.is_floating_point() else y
+
+
+LN_MAX_D = 2048  # widest row of ln_fwd_kernel / ln_bwd_kernel (4 chunks of 512)
 
 
 class _LNFn(torch.autograd.Function):
@@ -156,12 +166,15 @@ class _LNFn(torch.autograd.Function):
 def layer_norm(x, gamma, beta, eps=1e-5, link=None):
     """link: a ResidualGradLink shared with the residual add of the same input (ops.add_dropout(..., link=)):
     that add parks its gradient of x and this backward returns the sum (no autograd add kernel)."""
-    if on_gpu(x) and x.shape[-1] % 8 == 0 and x.dtype == BF16:
+    # the kernels hold a row in registers: D % 8 == 0 and D <= LN_MAX_D (norm.hip LN_DISPATCH); other widths take
+    # the PyTorch path below
+    kernel_ok = on_gpu(x) and x.shape[-1] % 8 == 0 and x.shape[-1] <= LN_MAX_D
+    if kernel_ok and x.dtype == BF16:
         return _LNFn.apply(x, gamma, beta, float(eps), link)
     pend = take_pending(x)
     if pend is not None:  # (an input this LayerNorm cannot fuse: form the sum first)
         pend.resolve(x)
-    if on_gpu(x) and x.shape[-1] % 8 == 0:
+    if kernel_ok:
         return _LNFn.apply(x.to(BF16), gamma, beta, float(eps), link)
     return torch.nn.functional.layer_norm(x.float(), (x.shape[-1],), gamma, beta, eps).to(
         x.dtype if x.is_floating_point() else torch.float32)

@@ -134,3 +134,140 @@ def attention_f64(q, k, v, do, causal=False, mask=None, scale=None, keep_mask=No
     o = torch.matmul(p, v)
     dq, dk, dv = torch.autograd.grad(o, [q, k, v], do.double())
     return o.detach(), dq, dk, dv, lse2, dead
+
+
+# ------------------------------------------------------------------ per-channel helpers (batch norm, pooling)
+def check_chans(name, out, ref, tol, worst=None, base=None):
+    """check_rows per CHANNEL of channels-last tensors: [..., C] is flattened to [M, C] and transposed, so err_c =
+    max_m |out - ref| / max(max_m |ref_c|, floor) with the same floor (one bf16 ulp of the tensor's largest value)."""
+    C = ref.shape[-1]
+    assert out.shape == ref.shape, (out.shape, ref.shape)
+    return check_rows(name, out.detach().reshape(-1, C).t(), ref.detach().reshape(-1, C).t(), tol, worst, base)
+
+
+def check_sums(name, out, ref, scale, tol=1e-4, worst=None):
+    """f32 per-channel reductions: |out_c - ref_c| <= tol * scale_c, scale_c the float64 sum of the absolute values of
+    channel c's terms (what an f32 summation in any order can lose). Records the worst |err| / scale."""
+    out, ref, scale = (t.detach().double().cpu().reshape(-1) for t in (out, ref, scale))
+    assert out.shape == ref.shape == scale.shape, (out.shape, ref.shape, scale.shape)
+    assert torch.isfinite(out).all(), f"{name}: non-finite output"
+    err = (out - ref).abs()
+    ratio = err / scale.clamp_min(1e-300)
+    ratio = torch.where(err == 0, torch.zeros_like(ratio), ratio)
+    w = ratio.max().item() if ratio.numel() else 0.0
+    print(f"  {name}: worst |err| / scale {w:.3e} (bound {tol:.1e})")
+    if worst is not None:
+        worst[name] = max(worst.get(name, 0.0), w)
+    bad = torch.nonzero(err > tol * scale)
+    assert bad.numel() == 0, (f"{name}: channel {bad[0].item()} off by {err[bad[0]].item():.3e} > "
+                              f"{tol:.1e} * {scale[bad[0]].item():.3e}")
+    return w
+
+
+def _pair(v):
+    return (v, v) if isinstance(v, int) else tuple(v)
+
+
+def _pool_geo(H, W, k, s, p):
+    (R, S), (sh, sw), (ph, pw) = _pair(k), _pair(s), _pair(p)
+    return R, S, sh, sw, ph, pw, (H + 2 * ph - R) // sh + 1, (W + 2 * pw - S) // sw + 1
+
+
+def maxpool_first(x, k, s, p):
+    """Max pool of a channels-last [N,H,W,C] tensor with -inf padding. The taps are walked in (r, s) order and a
+    later tap replaces the best only when strictly greater: the FIRST maximal tap wins, maxpool_fwd_kernel's rule
+    (nothing here depends on how PyTorch breaks ties). Returns (values in x's dtype, tap index r*S+s as int64),
+    both [N,P,Q,C]."""
+    N, H, W, C = x.shape
+    R, S, sh, sw, ph, pw, P, Q = _pool_geo(H, W, k, s, p)
+    xp = torch.full((N, H + 2 * ph, W + 2 * pw, C), NEG, dtype=torch.float64, device=x.device)
+    xp[:, ph:ph + H, pw:pw + W] = x.double()
+    best = torch.full((N, P, Q, C), NEG, dtype=torch.float64, device=x.device)
+    idx = torch.zeros((N, P, Q, C), dtype=torch.int64, device=x.device)
+    for r in range(R):
+        for c in range(S):
+            v = xp[:, r:r + (P - 1) * sh + 1:sh, c:c + (Q - 1) * sw + 1:sw]
+            upd = v > best
+            best = torch.where(upd, v, best)
+            idx = torch.where(upd, torch.full_like(idx, r * S + c), idx)
+    return best.to(x.dtype), idx
+
+
+def maxpool_scatter(dy, idx, H, W, k, s, p):
+    """float64 gradient of maxpool_first: every pooled gradient goes to the input pixel its tap index names."""
+    N, P, Q, C = dy.shape
+    R, S, sh, sw, ph, pw, P2, Q2 = _pool_geo(H, W, k, s, p)
+    assert (P, Q) == (P2, Q2), (P, Q, P2, Q2)
+    dxp = torch.zeros((N, H + 2 * ph, W + 2 * pw, C), dtype=torch.float64, device=dy.device)
+    for r in range(R):
+        for c in range(S):
+            dxp[:, r:r + (P - 1) * sh + 1:sh, c:c + (Q - 1) * sw + 1:sw] += dy.double() * (idx == r * S + c)
+    return dxp[:, ph:ph + H, pw:pw + W].contiguous()
+
+
+class BNRef:
+    """Result of bn_f64 (float64 CPU tensors; the backward fields are None without dy)."""
+    y = mean = var = invstd = xhat = mask = None
+    dz = dx = dgamma = dbeta = dres = dgamma_scale = dbeta_scale = None
+
+
+def bn_f64(x, gamma, beta, eps, res=None, relu=False, dy=None):
+    """float64 training batch norm over all but the last axis of the (already bf16-rounded) x, y = [relu](gamma * xhat
+    + beta [+ res]), and for a given dy its gradients: dz = dy where the ReLU passed, dbeta = sum dz, dgamma = sum
+    dz * xhat, dx = gamma * invstd * (dz - dbeta / M - xhat * dgamma / M), dres = dz. The ReLU mask is taken from the
+    bf16-rounded output, as the kernel's mask bits are (f2bf(o) != 0 && o > 0). var is the biased batch variance;
+    dgamma_scale / dbeta_scale are the sums of |terms| for check_sums."""
+    o = BNRef()
+    xd = x.detach().double().cpu()
+    C = xd.shape[-1]
+    x2 = xd.reshape(-1, C)
+    M = x2.shape[0]
+    g = torch.ones(C, dtype=torch.float64) if gamma is None else gamma.detach().double().cpu()
+    b = torch.zeros(C, dtype=torch.float64) if beta is None else beta.detach().double().cpu()
+    o.mean = x2.mean(0)
+    o.var = ((x2 - o.mean) ** 2).mean(0)
+    o.invstd = torch.rsqrt(o.var + eps)
+    o.xhat = (x2 - o.mean) * o.invstd
+    y = o.xhat * g + b
+    if res is not None:
+        y = y + res.detach().double().cpu().reshape(-1, C)
+    o.mask = torch.ones_like(y, dtype=torch.bool)
+    if relu:
+        y = torch.relu(y)
+        o.mask = bf16_round(y) > 0
+    o.y = y.reshape(xd.shape)
+    if dy is not None:
+        dz = dy.detach().double().cpu().reshape(-1, C) * o.mask
+        o.dbeta, o.dbeta_scale = dz.sum(0), dz.abs().sum(0)
+        o.dgamma, o.dgamma_scale = (dz * o.xhat).sum(0), (dz * o.xhat).abs().sum(0)
+        o.dx = (g * o.invstd * (dz - o.dbeta / M - o.xhat * o.dgamma / M)).reshape(xd.shape)
+        o.dz = dz.reshape(xd.shape)
+        o.dres = o.dz if res is not None else None
+    return o
+
+
+# (H, W, kernel, stride, pad) of the max-pool edge tests: odd maps, pad 0, overlapping stride-1 windows, stride ==
+# kernel, the 1x1 identity and a rectangular window with rectangular stride / pad
+POOL_GEOS = [(7, 7, 3, 2, 1), (8, 6, 2, 2, 0), (5, 9, 3, 1, 1), (6, 6, 3, 3, 0), (4, 4, 1, 1, 0),
+             (9, 7, (3, 2), (2, 1), (1, 0))]
+
+
+def maxpool_unique(x, k, s, p):
+    """[N,P,Q,C] bool: exactly one tap of the window holds its maximum (the winning tap does not depend on a tie rule)."""
+    N, H, W, C = x.shape
+    R, S, sh, sw, ph, pw, P, Q = _pool_geo(H, W, k, s, p)
+    xp = torch.full((N, H + 2 * ph, W + 2 * pw, C), NEG, dtype=torch.float64, device=x.device)
+    xp[:, ph:ph + H, pw:pw + W] = x.double()
+    best = maxpool_first(x, k, s, p)[0].double()
+    n = torch.zeros((N, P, Q, C), dtype=torch.int64, device=x.device)
+    for r in range(R):
+        for c in range(S):
+            n += xp[:, r:r + (P - 1) * sh + 1:sh, c:c + (Q - 1) * sw + 1:sw] == best
+    return n == 1
+
+
+def chan_base(ref):
+    """Worst per-channel err of the float64 reference rounded to bf16: what bf16 storage alone costs."""
+    C = ref.shape[-1]
+    r = ref.detach().double().cpu().reshape(-1, C).t()
+    return row_err(bf16_round(r), r).max().item()
