@@ -32,10 +32,12 @@ def gemm(a, b, *, a_kouter=False, b_kouter=False, out=None, out_dtype=BF16, bias
     padded = _pad_operands(a, b, a_kouter, b_kouter)
     if padded is not None:
         a2, b2, M, N = padded
+        Mp, Np = a2.shape[-1 if a_kouter else -2], b2.shape[-1 if b_kouter else -2]
+        # the pre-activation side output is padded like the output (the kernel writes both with one row stride)
+        aux2 = None if aux is None else torch.empty(a2.shape[:-2] + (Mp, Np), dtype=BF16, device=a.device)
         o = gemm(a2, b2, a_kouter=a_kouter, b_kouter=b_kouter, out_dtype=out_dtype if out is None else out.dtype,
-                 bias=None if bias is None else torch.nn.functional.pad(bias, (0, b2.shape[-1 if b_kouter else -2]
-                                                                               - N)),
-                 act=act, alpha=alpha, splitk=splitk, tile=tile)
+                 bias=None if bias is None else torch.nn.functional.pad(bias, (0, Np - N)),
+                 act=act, alpha=alpha, aux=aux2, splitk=splitk, tile=tile)
         o = o[..., :M, :N]
         if stats is not None:
             y = o.float()
@@ -43,7 +45,7 @@ def gemm(a, b, *, a_kouter=False, b_kouter=False, out=None, out_dtype=BF16, bias
             stats[:N] += y.sum(red)
             stats[N:] += (y * y).sum(red)
         if aux is not None:
-            raise NotImplementedError("aux output with padded gemm")
+            aux.copy_(aux2[..., :M, :N])
         if out is None:
             return o.contiguous()
         if beta != 0:
@@ -238,8 +240,17 @@ class _DenseFn(torch.autograd.Function):
         src = ctx.src
         ctx.src = None
         if ctx.act and not (src is not None and src.fused_ptr == dy2.data_ptr()):
-            dz = torch.empty_like(dy2)
-            call("dtf_act", ptr(pre), ptr(dy2), ptr(dz), dz.numel(), ctx.act, 1, stream())
+            n = dy2.numel()
+            if n % 8:  # the kernel works on whole 16-B chunks: zero-pad the flat tensors (act'(0) * 0 = 0)
+                pad = (0, -n % 8)
+                p8 = torch.nn.functional.pad(pre.reshape(-1), pad)
+                g8 = torch.nn.functional.pad(dy2.reshape(-1), pad)
+                d8 = torch.empty_like(g8)
+                call("dtf_act", ptr(p8), ptr(g8), ptr(d8), d8.numel(), ctx.act, 1, stream())
+                dz = d8[:n].view_as(dy2)
+            else:
+                dz = torch.empty_like(dy2)
+                call("dtf_act", ptr(pre), ptr(dy2), ptr(dz), n, ctx.act, 1, stream())
         else:
             dz = dy2  # (the consumer's data-gradient GEMM already applied act')
         dx = dw = db = None
