@@ -13,8 +13,8 @@ import os
 
 import torch
 
-from ._util import (BF16, F32, SIDE_STREAM_ON, IntOut, K as K_, before_overwrite, bf16_shadow, call, crsk_shadow,
-                    direct_grad, fork_side, mark_parked, on_gpu, ptr, stream, workspace)
+from ._util import (BF16, F32, SIDE_STREAM_ON, IntOut, K as K_, before_overwrite, bf16_shadow, call, contig,
+                    crsk_shadow, direct_grad, fork_side, mark_parked, on_gpu, ptr, stream, workspace)
 
 
 def out_size(h, k, s, p, d=1):
@@ -40,19 +40,28 @@ def _geom(x, w, stride, pad, dil):
     return N, H, W, C, K, R, S, P, Q, sh, sw, ph, pw, dh, dw
 
 
+def _partial_rows(want, cap, width, device):
+    """Up to `cap` BatchNorm partial-sum rows ([2 * width] f32) for a kernel epilogue to write: the buffer, the row
+    counter the launch fills in and the (pointer, counter address) pair to launch with; Nones when not wanted."""
+    if not want:
+        return None, None, (None, None)
+    part, rows = torch.empty(cap * 2 * width, dtype=F32, device=device), IntOut()
+    return part, rows, (ptr(part), rows.addr)
+
+
+def _bn_ptrs(bn):
+    """Pointers of a _BNSource's BN input (materialised first if it was not stored), ReLU bits and batch mean."""
+    return (ptr(bn.materialize()), ptr(bn.mbits), ptr(bn.mean)) if bn is not None else (None, None, None)
+
+
 def conv_fwd_raw(x, w16, g, stats=False, bias=None, act=0):
     """Returns y, or (y, partials, rows) when stats: BN partial sums, one [2K] row per M-tile."""
     N, H, W, C, K, R, S, P, Q, sh, sw, ph, pw, dh, dw = g
     y = torch.empty((N, P, Q, K), dtype=BF16, device=x.device)
-    part = rows = None
-    if stats:
-        part = torch.empty(((N * P * Q + 63) // 64) * 2 * K, dtype=F32, device=x.device)
-        rows = IntOut()
-    call("dtf_conv_fwd", ptr(x), ptr(w16), ptr(y), ptr(bias), ptr(part), rows.addr if rows else None, N, H, W, C,
-         K, R, S, P, Q, sh, sw, ph, pw, dh, dw, int(act), 0, -1, stream())
-    if stats:
-        return y, part, rows.value
-    return y
+    part, rows, row_args = _partial_rows(stats, (N * P * Q + 63) // 64, K, x.device)
+    call("dtf_conv_fwd", ptr(x), ptr(w16), ptr(y), ptr(bias), *row_args, N, H, W, C, K, R, S, P, Q, sh, sw, ph, pw, dh,
+         dw, int(act), 0, -1, stream())
+    return (y, part, rows.value) if stats else y
 
 
 def conv_fwd_bn_raw(x, w16, g, gamma, beta, rmean, rvar, momentum, eps, scale, shift, mean, invstd):
@@ -78,26 +87,25 @@ def conv_dgrad_raw(dy, w_master, g, acc=None, bn=None, acc_mask=None, acc_sub2=N
     wc = crsk_shadow(w_master, K, R * S, C)
     dx = torch.empty((N, H, W, C), dtype=BF16, device=dy.device) if acc is None else acc
     ws = workspace(dy.device)  # strided convs: per-phase compact filters (bf16) live here
-    part = rows = None
-    if bn is not None:
-        # one partial row per M-tile (>= 64 rows) of every launch: a strided dgrad runs sh*sw phase launches,
-        # each of which may end in a partial tile
-        part = torch.empty(((N * H * W + 63) // 64 + sh * sw) * 2 * C, dtype=F32, device=dy.device)
-        rows = IntOut()
-    bn_ptrs = ((ptr(bn.yc), ptr(bn.mbits), ptr(bn.mean)) if bn is not None else (None, None, None))
+    # one partial row per M-tile (>= 64 rows) of every launch: a strided dgrad runs sh*sw phase launches, each of
+    # which may end in a partial tile
+    part, rows, row_args = _partial_rows(bn is not None, (N * H * W + 63) // 64 + sh * sw, C, dy.device)
     if acc_sub2 is not None:  # + the compact gradient of a stride-2 1x1 shortcut at the even pixels
         assert acc is None and (R, S, sh, sw, ph, pw) == (1, 1, 1, 1, 0, 0)
-    rx = (ptr(bn.rx), ptr(bf16_shadow(bn.rw))) if (bn is not None and bn.yc is None) else (None, None)
     args = (ptr(dy), ptr(wc), ptr(dx), N, H, W, C, K, R, S, P, Q, sh, sw, ph, pw, dh, dw,
             1.0 if (acc is not None or acc_sub2 is not None) else 0.0, ptr(ws), 2 * ws.numel())
-    tail = (ptr(part), rows.addr if rows else None, ptr(acc_mask) if acc is not None else None, ptr(acc_sub2))
-    rc = K_().dtf_conv_dgrad_x(*args, None, ptr(bn.mbits), ptr(bn.mean), *tail, *rx, stream()) if rx[0] else -12
-    if rc == -12:  # (the BN input is stored, or only the persistent pointwise route can recompute it)
-        if bn is not None:
-            bn_ptrs = (ptr(bn.materialize()), ptr(bn.mbits), ptr(bn.mean))
-        call("dtf_conv_dgrad_x", *args, *bn_ptrs, *tail, None, None, stream())
-    elif rc != 0:
-        raise RuntimeError(f"dtf_conv_dgrad_x failed with status {rc}")
+    tail = (*row_args, ptr(acc_mask) if acc is not None else None, ptr(acc_sub2))
+    recomputed = False
+    if bn is not None and bn.yc is None:
+        # the BN input was not stored: the launch recomputes it per tile from the producer's input and filter, or
+        # answers -12 without launching when the shape's route cannot (only the persistent pointwise route can)
+        rc = K_().dtf_conv_dgrad_x(*args, None, ptr(bn.mbits), ptr(bn.mean), *tail, ptr(bn.rx),
+                                   ptr(bf16_shadow(bn.rw)), stream())
+        if rc not in (0, -12):
+            raise RuntimeError(f"dtf_conv_dgrad_x failed with status {rc}")
+        recomputed = rc == 0
+    if not recomputed:
+        call("dtf_conv_dgrad_x", *args, *_bn_ptrs(bn), *tail, None, None, stream())
     if bn is not None:
         bn.provide(dx, part, rows.value)
     return dx
@@ -109,9 +117,8 @@ def _recompute_y(x, w, g):
     N, H, W, C, K = g[:5]
     M = N * H * W
     y = torch.empty((N, H, W, K), dtype=BF16, device=x.device)
-    stats = torch.empty(((M + 63) // 64) * 2 * K, dtype=F32, device=x.device)
-    rows = IntOut()
-    call("dtf_pwconv_fwd", ptr(x), ptr(bf16_shadow(w)), ptr(y), ptr(stats), rows.addr, M, C, K, stream())
+    stats, _, row_args = _partial_rows(True, (M + 63) // 64, K, x.device)  # (always written; not used here)
+    call("dtf_pwconv_fwd", ptr(x), ptr(bf16_shadow(w)), ptr(y), *row_args, M, C, K, stream())
     return y
 
 
@@ -143,13 +150,9 @@ def conv_bwd_fused_raw(dy, x, w_master, g, dw_out, bn=None):
     wc = crsk_shadow(w_master, K, 1, C)
     dx = torch.empty((N, H, W, C), dtype=BF16, device=dy.device)
     ws = workspace(dy.device)
-    part = rows = None
-    if bn is not None:
-        part = torch.empty(256 * 2 * C, dtype=F32, device=dy.device)
-        rows = IntOut()
-    bn_ptrs = ((ptr(bn.materialize()), ptr(bn.mbits), ptr(bn.mean)) if bn is not None else (None, None, None))
-    call("dtf_pw_conv_bwd", ptr(dy), ptr(x), ptr(wc), ptr(dx), ptr(dw_out), 1, *bn_ptrs, ptr(part),
-         rows.addr if rows else None, ptr(ws), ws.numel(), M, K, C, stream())
+    part, rows, row_args = _partial_rows(bn is not None, 256, C, dy.device)  # (<= 256 pixel slots)
+    call("dtf_pw_conv_bwd", ptr(dy), ptr(x), ptr(wc), ptr(dx), ptr(dw_out), 1, *_bn_ptrs(bn), *row_args, ptr(ws),
+         ws.numel(), M, K, C, stream())
     if bn is not None:
         bn.provide(dx, part, rows.value)
     return dx
@@ -159,29 +162,23 @@ def conv_bwd_bn_fused_raw(dout, y, ymask, coef, x, w_master, g, dw_out, bn=None,
     """conv_bwd_fused_raw with dy = a*dz + b*y + c (the BatchNorm(+ReLU) backward of y = conv output, coefficients
     coef [3K] from dtf_bn_bwd_coef, dz = dout under the ReLU bits ymask) computed inside the kernel. With `sc` (the
     _BNSource of a deferred projection-shortcut BN added as this layer's residual) the kernel also takes that BN's
-    backward reduction of dz and provides it to the source for `dout`. With `wy` (the layer's bf16 forward filter) and
-    y None, y is recomputed per tile from x (it was not stored).""" 
+    backward reduction of dz and provides it to the source for `dout`, together with ymask: the shortcut's backward then
+    receives the raw dout and applies the ReLU bits itself (no dz is materialised). With `wy` (the layer's bf16 forward
+    filter) and y None, y is recomputed per tile from x (it was not stored)."""
     N, H, W, C, K = g[:5]
     M = N * H * W
     wc = crsk_shadow(w_master, K, 1, C)
     dx = torch.empty((N, H, W, C), dtype=BF16, device=dout.device)
     ws = workspace(dout.device)
-    part = rows = None
-    if bn is not None:
-        part = torch.empty(256 * 2 * C, dtype=F32, device=dout.device)  # (<= 256 pixel slots)
-        rows = IntOut()
-    bn_ptrs = ((ptr(bn.materialize()), ptr(bn.mbits), ptr(bn.mean)) if bn is not None else (None, None, None))
-    psc = rsc = None
-    if sc is not None:
-        psc, rsc = torch.empty(256 * 2 * K, dtype=F32, device=dout.device), IntOut()
+    part, rows, row_args = _partial_rows(bn is not None, 256, C, dout.device)  # (<= 256 pixel slots)
+    psc, rsc, sc_args = _partial_rows(sc is not None, 256, K, dout.device)
+    sc_ptrs = (ptr(sc.yc), ptr(sc.mean)) if sc is not None else (None, None)
     call("dtf_pw_conv_bwd_bn", ptr(dout), ptr(y), ptr(ymask), ptr(coef), ptr(x), ptr(wc), ptr(dx), ptr(dw_out), 1,
-         *bn_ptrs, ptr(part), rows.addr if rows else None, ptr(ws), ws.numel(), M, K, C,
-         ptr(sc.yc) if sc is not None else None, ptr(sc.mean) if sc is not None else None, ptr(psc),
-         rsc.addr if rsc else None, ptr(wy), stream())
+         *_bn_ptrs(bn), *row_args, ptr(ws), ws.numel(), M, K, C, *sc_ptrs, *sc_args, ptr(wy), stream())
     if bn is not None:
         bn.provide(dx, part, rows.value)
     if sc is not None:
-        sc.provide(dout, psc, rsc.value)
+        sc.provide(dout, psc, rsc.value, mask=ymask)
     return dx
 
 
@@ -320,14 +317,14 @@ class _BNSource:
     backward then skips its reduction pass (bn_bwd_reduce), provided the gradient it receives is exactly the
     tensor that dgrad wrote (same storage: autograd added nothing else to it)."""
     __slots__ = ("yc", "mbits", "mean", "invstd", "gamma", "gamma_p", "beta_p", "consumers", "part", "rows", "dx",
-                 "ver", "rx", "rw", "g", "__weakref__")
+                 "ver", "mask", "rx", "rw", "g", "__weakref__")
 
     def __init__(self, yc, mbits, mean, invstd=None, gamma=None, params=(None, None), recompute=None):
         self.yc, self.mbits, self.mean = yc, mbits, mean
         self.invstd, self.gamma = invstd, gamma
         self.gamma_p, self.beta_p = params
         self.consumers = 0
-        self.part = self.rows = self.dx = self.ver = None
+        self.part = self.rows = self.dx = self.ver = self.mask = None
         # yc not stored: it is bf16(rx rw^T), the producing 1x1 conv's output (input rx, filter parameter rw, geometry
         # g), recomputed by the consumers that can (pwconv.hip RX, pwbwd.hip YR) or materialised on demand
         self.rx, self.rw, self.g = recompute if recompute is not None else (None, None, None)
@@ -338,20 +335,27 @@ class _BNSource:
             self.yc = _recompute_y(self.rx, self.rw, self.g)
         return self.yc
 
-    def provide(self, dx, part, rows):
+    def provide(self, dx, part, rows, mask=None):
+        """The producer of this BN's output gradient `dx` records the reduction rows it took of it, and `mask`, the
+        ReLU bits still to apply to dx when it hands over a raw (unmasked) gradient."""
         # dx itself is held (not its address), with its version: see nn.same_unmodified
-        self.part, self.rows, self.dx, self.ver = part, rows, dx, dx._version
+        self.part, self.rows, self.dx, self.ver, self.mask = part, rows, dx, dx._version, mask
 
     def take(self, dout):
-        """("partials", part, rows) for this gradient, or None (then the regular reduction runs)."""
+        """For the gradient `dout` this BN's backward received: ((part, rows) or None (then the regular reduction
+        runs), the ReLU bits still to apply to dout or None). Rows recorded for another tensor are dropped; a mask
+        recorded for another tensor is an error (dout would be taken for an already masked gradient)."""
         from .nn import same_unmodified
-        part, rows, dx, ver = self.part, self.rows, self.dx, self.ver
-        self.part = self.rows = self.dx = self.ver = None
+        part, rows, dx, ver, mask = self.part, self.rows, self.dx, self.ver, self.mask
+        self.part = self.rows = self.dx = self.ver = self.mask = None
         if not same_unmodified(dout, dx, ver):
-            return None
-        if part is None or rows < 1:
-            return None
-        return "partials", part, rows
+            if mask is not None:
+                raise RuntimeError(
+                    "the projection shortcut's gradient was replaced or modified between the block's last conv and "
+                    "the projection (a tensor hook that returns a new gradient, or a second consumer of the shortcut "
+                    "whose gradient autograd added): the last conv handed over its raw gradient and the ReLU mask")
+            return None, None
+        return (part, rows) if part is not None and rows >= 1 else None, mask
 
 
 # Fused BatchNorm backward reduction in the consumer's data-gradient GEMM (see _BNSource), lazy residual gradient
@@ -365,12 +369,10 @@ _COMPACT_PROJ = True
 # epilogue, pwconv.hip dtf_conv_bn_apply_fwd) instead of conv(+stats) -> finalize -> standalone apply pass.
 _TWO_PASS_PW = os.environ.get("DTF_PW2", "1") != "0"
 # Fused data + weight gradient of the stage-1 channel-reducing 1x1 convs (pwbwd.hip): one read of dY for both,
-# the weight gradient on the main stream instead of the side stream.
-# Level 2 also folds the conv output's BatchNorm(+ReLU) backward into that pass when its reduction is already done
-# (identity blocks: dY = a dz + b y + c computed per tile, never stored: the standalone apply pass disappears).
-# Level 3 stops storing the stage-1 identity blocks' c3 output y at all: the folded pass and the next
-# block's c1 data gradient recompute it per tile from the c3 input (bitwise the forward's values); level 4 (default) also the
-# projection block's.
+# the weight gradient on the main stream instead of the side stream. Level 2 also folds the conv output's
+# BatchNorm(+ReLU) backward into that pass when its reduction is already done (dY = a dz + b y + c computed per tile,
+# never stored: the standalone apply pass disappears; see bwd_route). Levels 3 and 4 (default) stop storing stage-1 c3
+# outputs at all: their consumers recompute them per tile, bitwise the forward's values (see _keep_y).
 _FUSED_PW_BWD = int(os.environ.get("DTF_PW_BWD", "4"))
 
 
@@ -385,6 +387,72 @@ def _two_pass_ok(g):
 # (Measured and removed: "lazy" BatchNorm outputs applied by the consuming conv's operand loaders, r3 —
 # profiles/r3_lazy_bn_modes.txt; the BN finalize inside the producing GEMM launch and a BN apply that recomputes the
 # expanding 1x1 product, r4 — profiles/r4_negative_results.txt.)
+
+
+def _keep_y(g, relu, has_res, res_deferred, link_given, role, needs_grad, level=None):
+    """Whether the two-pass forward stores the conv output y. Level 3 does not store a stage-1 identity block's c3
+    output: its consumers (the layer's BatchNorm-folded backward, the next block's c1 data gradient) recompute it
+    from x and w; level 4 neither the projection block's (`res_deferred`: the residual is a deferred projection BN)."""
+    level = _FUSED_PW_BWD if level is None else level
+    N, H, W, C, K, R, S, P, Q = g[:9]
+    return not (level >= 3 and (C, K) == (64, 256) and relu and has_res and N * P * Q >= 64 * 256 and needs_grad
+                and ((not res_deferred and link_given and role == "res") or (level >= 4 and res_deferred)))
+
+
+def _lazy_res(has_res, relu, role, link_open, relu_bits):
+    """Identity shortcut with ReLU: dout is parked on the link with the ReLU mask, no masked gradient is written."""
+    return bool(has_res and relu and role == "res" and link_open and _LAZY_RES and relu_bits)
+
+
+def _bn_complete(consumers, role, acc_taken=False):
+    """Whether a conv's dX is the COMPLETE gradient of its input BatchNorm's output (see _BNSource): it is the only
+    consumer, or the "acc" conv that took the second consumer's parked gradient to add into. Never a projection,
+    whose dX is joined with the first conv's. (Only the general route takes an acc; fold_identity has role "res".)"""
+    return role != "proj" and (consumers == 1 or (role == "acc" and acc_taken and consumers == 2))
+
+
+def bwd_route(g, role, relu, has_res, training, *, link_open, relu_bits, rows_taken, shortcut_src, yc_stored,
+              mask_given, need_dx, need_dw, direct_w, x_bf16, level=None):
+    """The route _ConvBNFn.backward takes, from facts alone (no tensors, no launches; level: _FUSED_PW_BWD unless
+    given). rows_taken: the consumer's BN-backward partial rows were taken for this gradient; shortcut_src: a deferred
+    projection-shortcut BN rides on this layer; mask_given: the gradient came with ReLU bits still to apply; direct_w:
+    a direct weight-gradient view exists; x_bf16: x is contiguous bf16.
+
+    fold_* (level >= 2, the BN reduction already taken): only the BN-backward coefficients are finalized, then ONE
+    pass forms dY per tile and computes dX and dW from it (dtf_pw_conv_bwd_bn) — an identity block's c3, the stage-1
+    projection block's c3 (taking the shortcut BN's reduction too), that block's stride-1 projection. Otherwise the
+    standalone BN backward runs, then pw_fused (level >= 1: dX, dW in one pass over dY, dtf_pw_conv_bwd) or general."""
+    level = _FUSED_PW_BWD if level is None else level
+    if not training:
+        return "frozen"
+    stage1 = (g[4], g[3]) == (256, 64)
+    if level >= 2 and rows_taken and need_dx and need_dw and x_bf16 and direct_w and pw_bwd_bn_ok(g):
+        if _lazy_res(has_res, relu, role, link_open, relu_bits) and not shortcut_src and (yc_stored or stage1):
+            return "fold_identity"
+        if shortcut_src and relu and stage1:
+            return "fold_proj_block"
+        if yc_stored and mask_given and role == "proj" and not shortcut_src and stage1:
+            return "fold_shortcut"
+    if level >= 1 and need_dw and direct_w and need_dx and role != "acc" and pw_bwd_ok(g) and x_bf16:
+        return "pw_fused"
+    return "general"
+
+
+def _bn_grad_targets(bn_params, K, device):
+    """(dgamma, dbeta, direct) for a backward to write: the parameters' arena gradient views when both exist (then
+    accumulated in place, direct), else fresh [K] buffers."""
+    tg, tb = (direct_grad(p) for p in bn_params)
+    if tg is not None and tb is not None:
+        return tg, tb, True
+    return torch.empty(K, dtype=F32, device=device), torch.empty(K, dtype=F32, device=device), False
+
+
+def _grads(dx, dw, dgamma, dbeta, dres=None, direct_bn=False):
+    """What _ConvBNFn / _ConvBNPoolFn.backward return: a slot per forward argument, (x, w, gamma, beta[, residual])
+    first, no gradient for the rest; dgamma / dbeta accumulated in place (direct_bn) are not handed to autograd."""
+    if direct_bn:
+        dgamma = dbeta = None
+    return (dx, dw, dgamma, dbeta, dres) + (None,) * (_FWD_ARGS - 5)
 
 
 class _ConvBNFn(torch.autograd.Function):
@@ -406,53 +474,43 @@ class _ConvBNFn(torch.autograd.Function):
         work = torch.empty(4 * K, dtype=F32, device=dev)  # scale shift mean invstd
         scale, shift, mean, invstd = work[:K], work[K:2 * K], work[2 * K:3 * K], work[3 * K:]
         raff = getattr(res, "_dtf_affine", None) if res is not None else None
-        deferred = role == "proj" and not relu and _DEFER_PROJ_BN
-        out = mbits = None
-        if training and not deferred and _TWO_PASS_PW and _two_pass_ok(g):
-            # channel-expanding 1x1 (bottleneck c3): statistics pass, finalize, then the recomputed product with the
-            # BatchNorm / residual / ReLU applied in the epilogue (pwconv.hip MODE 1 / 2) — no standalone apply pass
-            # level 3: an identity block's stage-1 c3 output is not stored at all — its consumers (this layer's
-            # BatchNorm-folded backward, the next block's c1 data gradient) recompute it from x and w
-            keep_y = not (_FUSED_PW_BWD >= 3 and (C, K) == (64, 256) and relu and res is not None
-                          and M >= 64 * 256 and any(ctx.needs_input_grad)
-                          and ((raff is None and link is not None and role == "res")
-                               or (_FUSED_PW_BWD >= 4 and raff is not None)))
-            yc = torch.empty((N, P, Q, K), dtype=BF16, device=dev) if keep_y else None
-            out = torch.empty((N, P, Q, K), dtype=BF16, device=dev)
-            mbits = torch.empty(M * K // 8, dtype=torch.uint8, device=dev) if relu else None
-            part = torch.empty(((M + 63) // 64) * 2 * K, dtype=F32, device=dev)
-            rc_ = res.contiguous() if res is not None else None
-            call("dtf_conv_bn_apply_fwd", ptr(x), ptr(bf16_shadow(w)), ptr(yc), ptr(out), ptr(mbits), ptr(rc_),
-                 ptr(raff[0]) if raff else None, ptr(raff[1]) if raff else None, M, C, K, int(relu), ptr(part),
-                 ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar), float(momentum), float(eps), ptr(scale), ptr(shift),
-                 ptr(mean), ptr(invstd), stream())
-        elif training:
-            yc = conv_fwd_bn_raw(x, bf16_shadow(w), g, gamma, beta, rmean, rvar, momentum, eps, scale, shift, mean,
-                                 invstd)
-        else:
-            yc = conv_fwd_raw(x, bf16_shadow(w), g)
-            call("dtf_bn_infer_coeff", ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar), K, float(eps), ptr(scale),
-                 ptr(shift), stream())
-            if any(ctx.needs_input_grad):  # frozen BN: the backward normalises with the running statistics
-                mean.copy_(rmean)
-                torch.rsqrt(rvar + eps, out=invstd)
+        raff_ptrs = (ptr(raff[0]), ptr(raff[1])) if raff else (None, None)
         # the deferred projection BN (its input + mean): its backward reduction is taken in our apply pass
         res_src = getattr(res, "_dtf_bnsrc", None) if raff is not None else None
-        if res is not None:
-            res = res.contiguous()
-        if out is not None:  # (the two-pass form above already wrote out and mbits)
-            pass
-        elif deferred:
-            # projection shortcut: its BN output is consumed only as the residual of the block's last ConvBN,
-            # whose apply pass normalises the conv output on the fly (res * scale + shift) — hand autograd the
-            # conv output tagged with the affine instead of materialising the BN output
-            out = yc
-            out._dtf_affine = (scale, shift)
+        res = contig(res)
+        deferred = role == "proj" and not relu and _DEFER_PROJ_BN
+        mbits = torch.empty(M * K // 8, dtype=torch.uint8, device=dev) if relu else None
+        if training and not deferred and _TWO_PASS_PW and _two_pass_ok(g):
+            # (bottleneck c3; BatchNorm / residual / ReLU applied in the epilogue: pwconv.hip MODE 1 / 2)
+            keep_y = _keep_y(g, relu, res is not None, raff is not None, link is not None, role,
+                             any(ctx.needs_input_grad))
+            yc = torch.empty((N, P, Q, K), dtype=BF16, device=dev) if keep_y else None
+            out = torch.empty((N, P, Q, K), dtype=BF16, device=dev)
+            part = torch.empty(((M + 63) // 64) * 2 * K, dtype=F32, device=dev)
+            call("dtf_conv_bn_apply_fwd", ptr(x), ptr(bf16_shadow(w)), ptr(yc), ptr(out), ptr(mbits), ptr(res),
+                 *raff_ptrs, M, C, K, int(relu), ptr(part), ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar),
+                 float(momentum), float(eps), ptr(scale), ptr(shift), ptr(mean), ptr(invstd), stream())
         else:
-            mbits = torch.empty(M * K // 8, dtype=torch.uint8, device=dev) if relu else None
-            out = torch.empty_like(yc)
-            call("dtf_bn_apply", ptr(yc), ptr(scale), ptr(shift), ptr(res), ptr(out), M, K, int(relu), ptr(mbits),
-                 ptr(raff[0]) if raff else None, ptr(raff[1]) if raff else None, stream())
+            if training:
+                yc = conv_fwd_bn_raw(x, bf16_shadow(w), g, gamma, beta, rmean, rvar, momentum, eps, scale, shift,
+                                     mean, invstd)
+            else:
+                yc = conv_fwd_raw(x, bf16_shadow(w), g)
+                call("dtf_bn_infer_coeff", ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar), K, float(eps), ptr(scale),
+                     ptr(shift), stream())
+                if any(ctx.needs_input_grad):  # frozen BN: the backward normalises with the running statistics
+                    mean.copy_(rmean)
+                    torch.rsqrt(rvar + eps, out=invstd)
+            if deferred:
+                # projection shortcut: its BN output is consumed only as the residual of the block's last ConvBN,
+                # whose apply pass normalises the conv output on the fly (res * scale + shift) — hand autograd the
+                # conv output tagged with the affine instead of materialising the BN output
+                out = yc
+                out._dtf_affine = (scale, shift)
+            else:
+                out = torch.empty_like(yc)
+                call("dtf_bn_apply", ptr(yc), ptr(scale), ptr(shift), ptr(res), ptr(out), M, K, int(relu),
+                     ptr(mbits), *raff_ptrs, stream())
         # backward needs the conv output and a 1-bit ReLU mask, not the bf16 BN output
         ctx.save_for_backward(x, w, gamma, yc, mbits, mean, invstd)
         ctx.bn_params = (gamma, beta)
@@ -465,139 +523,88 @@ class _ConvBNFn(torch.autograd.Function):
         ctx.res_src = res_src if (training and _FUSE_BN_BWD) else None
         ctx.src = None
         if training and _FUSE_BN_BWD and any(ctx.needs_input_grad):
-            src = _BNSource(yc, mbits, mean, invstd, gamma, (gamma, beta),
-                            recompute=(x, w, g) if yc is None else None)
-            out._dtf_bnsrc = src
-            ctx.src = src
+            ctx.src = out._dtf_bnsrc = _BNSource(yc, mbits, mean, invstd, gamma, (gamma, beta),
+                                                 recompute=(x, w, g) if yc is None else None)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         x, w, gamma, yc, mbits, mean, invstd = ctx.saved_tensors
         g = ctx.g
-        K = g[4]
-        M = g[0] * g[7] * g[8]
-        yshape, dev = (g[0], g[7], g[8], K), x.device
-        # a deferred projection BN whose consumer handed over its raw incoming gradient with the ReLU bits to apply
-        # (see the projection-block branch below): dz = dout under that mask
-        dmask = getattr(dout, "_dtf_mask", None)
+        N, H, W, C, K, R, S, P, Q, sh, sw, ph, pw = g[:13]
+        M = N * P * Q
+        yshape, dev = (N, P, Q, K), x.device
         dout = dout.to(BF16).contiguous()
+        taken, dmask = ctx.src.take(dout) if ctx.src is not None else (None, None)
         if dmask is not None:
+            # a deferred projection BN whose consumer folded (fold_proj_block): dout is raw, dz = dout under its mask
             assert mbits is None and not ctx.relu
             mbits = dmask
-        if not ctx.training:
-            return _ConvBNFn._backward_frozen(ctx, dout, x, w, gamma, yc, mbits, mean, invstd)
-        dyc = torch.empty(yshape, dtype=BF16, device=dev)
         link, role = ctx.link, ctx.role
-        # identity shortcut with ReLU: park dout + the ReLU mask instead of writing the masked residual gradient
-        lazy_res = (ctx.has_res and ctx.relu and link is not None and role == "res" and not link.closed
-                    and _LAZY_RES and mbits is not None)
-        dres = torch.empty(yshape, dtype=BF16, device=dev) if (ctx.has_res and ctx.relu and not lazy_res) else None
-        gamma_p, beta_p = ctx.bn_params
-        tg, tb = direct_grad(gamma_p), direct_grad(beta_p)
-        direct_bn = tg is not None and tb is not None  # accumulate dgamma/dbeta into the arena grads
-        dgamma = tg if direct_bn else torch.empty(K, dtype=F32, device=dev)
-        dbeta = tb if direct_bn else torch.empty(K, dtype=F32, device=dev)
-        fused = ctx.src.take(dout) if ctx.src is not None else None
-        rsrc = ctx.res_src if dres is not None else None
-        sc = (None, None, None, None)
-        if rsrc is not None:  # projection shortcut BN: its backward reduction rides on our apply pass
-            part2, rows2 = torch.empty(2048 * 2 * K, dtype=F32, device=dev), IntOut()
-            sc = (ptr(rsrc.yc), ptr(rsrc.mean), ptr(part2), rows2.addr)
-        if (fused is not None and lazy_res and rsrc is None and _FUSED_PW_BWD >= 2 and ctx.needs_input_grad[0]
-                and ctx.needs_input_grad[1] and pw_bwd_bn_ok(g) and x.is_contiguous() and x.dtype == BF16
-                and (yc is not None or (g[4], g[3]) == (256, 64))):
-            tw = direct_grad(w)
-            if tw is not None:
-                # identity-block c3: finalize the BN-backward reduction only, then ONE pass computes dY per tile from
-                # dout / yc / the ReLU bits and both conv gradients from it (dY is never stored)
-                coef = torch.empty(3 * K, dtype=F32, device=dev)
-                call("dtf_bn_bwd_coef", ptr(fused[1]), fused[2], ptr(mean), ptr(invstd), ptr(gamma), M, K,
-                     ptr(dgamma), ptr(dbeta), int(direct_bn), ptr(coef), stream())
-                src = ctx.in_src
-                complete = src is not None and src.consumers == 1
-                dx = conv_bwd_bn_fused_raw(dout, yc, mbits, coef, x, w, g, tw, bn=src if complete else None,
-                                           wy=bf16_shadow(w) if yc is None else None)
+        need_dx, need_dw = ctx.needs_input_grad[:2]
+        link_open = link is not None and not link.closed
+        lazy_res = _lazy_res(ctx.has_res, ctx.relu, role, link_open, mbits is not None)
+        want_dres = ctx.has_res and ctx.relu and not lazy_res  # (the masked residual gradient is written out)
+        rsrc = ctx.res_src if want_dres else None  # projection shortcut BN: its backward reduction rides on ours
+        tw = direct_grad(w) if need_dw else None
+        src = ctx.in_src
+
+        def complete_src(acc_taken=False):  # the input BN's source if our dX may take its backward reduction
+            return src if src is not None and _bn_complete(src.consumers, role, acc_taken) else None
+        route = bwd_route(g, role, ctx.relu, ctx.has_res, ctx.training, link_open=link_open,
+                          relu_bits=mbits is not None, rows_taken=taken is not None, shortcut_src=rsrc is not None,
+                          yc_stored=yc is not None, mask_given=dmask is not None, need_dx=need_dx, need_dw=need_dw,
+                          direct_w=tw is not None, x_bf16=x.is_contiguous() and x.dtype == BF16)
+        if route == "frozen":
+            return _ConvBNFn._backward_frozen(ctx, dout, x, w, gamma, yc, mbits, mean, invstd)
+        dgamma, dbeta, direct_bn = _bn_grad_targets(ctx.bn_params, K, dev)
+        if route.startswith("fold_"):
+            # dY is formed per tile from dout, the ReLU bits and yc (recomputed from x when not stored), never stored
+            coef = torch.empty(3 * K, dtype=F32, device=dev)
+            call("dtf_bn_bwd_coef", ptr(taken[0]), taken[1], ptr(mean), ptr(invstd), ptr(gamma), M, K, ptr(dgamma),
+                 ptr(dbeta), int(direct_bn), ptr(coef), stream())
+            dx = conv_bwd_bn_fused_raw(dout, yc, mbits, coef, x, w, g, tw, bn=complete_src(), sc=rsrc,
+                                       wy=bf16_shadow(w) if yc is None else None)
+            ctx.in_src = ctx.src = ctx.res_src = None
+            if route == "fold_identity":
                 # the identity shortcut's gradient: dout parked with the ReLU mask (read above, in stream order, before
                 # the first conv's dgrad overwrites it)
                 link.park(dout, mask=mbits)
-                ctx.in_src = ctx.src = ctx.res_src = None
-                if direct_bn:
-                    dgamma = dbeta = None
-                return (dx, None, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None,
-                        None)
-        blk_ok = (_FUSED_PW_BWD >= 2 and fused is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[1]
-                  and x.is_contiguous() and x.dtype == BF16)
-        if (blk_ok and rsrc is not None and not lazy_res and ctx.relu and pw_bwd_bn_ok(g)
-                and g[4] == 256 and g[3] == 64):
-            tw = direct_grad(w)
-            if tw is not None:
-                # projection-block c3 (stage 1): the same one-pass form, also taking the shortcut BN's reduction of
-                # dz; the shortcut then receives the raw dout tagged with the ReLU bits instead of a materialised dz
-                coef = torch.empty(3 * K, dtype=F32, device=dev)
-                call("dtf_bn_bwd_coef", ptr(fused[1]), fused[2], ptr(mean), ptr(invstd), ptr(gamma), M, K,
-                     ptr(dgamma), ptr(dbeta), int(direct_bn), ptr(coef), stream())
-                src = ctx.in_src
-                complete = src is not None and role != "proj" and src.consumers == 1
-                dx = conv_bwd_bn_fused_raw(dout, yc, mbits, coef, x, w, g, tw, bn=src if complete else None,
-                                           sc=rsrc, wy=bf16_shadow(w) if yc is None else None)
-                dout._dtf_mask = mbits
-                ctx.in_src = ctx.src = ctx.res_src = None
-                if direct_bn:
-                    dgamma = dbeta = None
-                return (dx, None, dgamma, dbeta, dout, None, None, None, None, None, None, None, None, None, None,
-                        None)
-        if (blk_ok and yc is not None and dmask is not None and role == "proj" and rsrc is None and pw_bwd_bn_ok(g)
-                and g[4] == 256 and g[3] == 64):
-            tw = direct_grad(w)
-            if tw is not None:
-                # the stride-1 projection of that block: its BN backward folded into its own gradient pass
-                coef = torch.empty(3 * K, dtype=F32, device=dev)
-                call("dtf_bn_bwd_coef", ptr(fused[1]), fused[2], ptr(mean), ptr(invstd), ptr(gamma), M, K,
-                     ptr(dgamma), ptr(dbeta), int(direct_bn), ptr(coef), stream())
-                dx = conv_bwd_bn_fused_raw(dout, yc, mbits, coef, x, w, g, tw)
-                if link is not None:
-                    dx = link.park(dx)
-                ctx.in_src = ctx.src = ctx.res_src = None
-                if direct_bn:
-                    dgamma = dbeta = None
-                return (dx, None, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None,
-                        None)
+            elif route == "fold_shortcut" and link is not None:
+                dx = link.park(dx)
+            # fold_proj_block: the shortcut receives the raw dout; its ReLU bits went to rsrc with the reduction rows
+            return _grads(dx, None, dgamma, dbeta, dout if route == "fold_proj_block" else None, direct_bn)
         if yc is None:  # (not stored by the forward and not recomputed inside a fused pass above)
             yc = _recompute_y(x, w, g)
-        if fused is not None:  # the consumer's dgrad epilogue already reduced this gradient
+        dyc = torch.empty(yshape, dtype=BF16, device=dev)
+        dres = torch.empty(yshape, dtype=BF16, device=dev) if want_dres else None
+        part2, rows2, sc_rows = _partial_rows(rsrc is not None, 2048, K, dev)
+        sc = ((ptr(rsrc.yc), ptr(rsrc.mean)) if rsrc is not None else (None, None)) + sc_rows
+        args = (ptr(mbits), ptr(yc), ptr(mean), ptr(invstd), ptr(gamma), M, K, ptr(dyc), ptr(dres), ptr(dgamma),
+                ptr(dbeta), int(direct_bn))
+        if taken is not None:  # the consumer's dgrad epilogue already reduced this gradient
             coef = torch.empty(3 * K, dtype=F32, device=dev)
-            call("dtf_bn_bwd_partials", ptr(dout), ptr(mbits), ptr(yc), ptr(mean), ptr(invstd), ptr(gamma), M, K,
-                 ptr(dyc), ptr(dres), ptr(dgamma), ptr(dbeta), int(direct_bn), ptr(fused[1]), fused[2], ptr(coef),
-                 *sc, stream())
+            call("dtf_bn_bwd_partials", ptr(dout), *args, ptr(taken[0]), taken[1], ptr(coef), *sc, stream())
         else:
             work = torch.empty((2 * 1024 + 3) * K, dtype=F32, device=dev)
-            call("dtf_bn_bwd", ptr(dout), None, ptr(mbits), ptr(yc), ptr(mean), ptr(invstd), ptr(gamma), M, K,
-                 ptr(dyc), ptr(dres), ptr(dgamma), ptr(dbeta), int(direct_bn), ptr(work), *sc, stream())
+            call("dtf_bn_bwd", ptr(dout), None, *args, ptr(work), *sc, stream())
         if rsrc is not None and rows2.value > 0:
             rsrc.provide(dres, part2, rows2.value)
-        ctx.res_src = None
-        ctx.src = None
+        ctx.res_src = ctx.src = None
         if ctx.has_res and not ctx.relu:
             dres = dout
         if lazy_res:
             dres = link.park(dout, mask=mbits)  # (None: parked; dout is overwritten by the first conv's dgrad)
         elif link is not None and role == "res":
             dres = link.park(dres)
-        dx = dw = None
-        tw = direct_grad(w) if ctx.needs_input_grad[1] else None
-        if (_FUSED_PW_BWD >= 1 and tw is not None and ctx.needs_input_grad[0] and role != "acc" and pw_bwd_ok(g)
-                and x.is_contiguous() and x.dtype == BF16):
-            src = ctx.in_src
-            complete = src is not None and role != "proj" and src.consumers == 1
-            dx = conv_bwd_fused_raw(dyc, x, w, g, tw, bn=src if complete else None)
+        if route == "pw_fused":
+            dx = conv_bwd_fused_raw(dyc, x, w, g, tw, bn=complete_src())
             if link is not None and role == "proj":
                 dx = link.park(dx)
             ctx.in_src = None
-            if direct_bn:
-                dgamma = dbeta = None
-            return dx, None, dgamma, dbeta, dres, None, None, None, None, None, None, None, None, None, None, None
-        if ctx.needs_input_grad[1]:
+            return _grads(dx, None, dgamma, dbeta, dres, direct_bn)
+        dx = dw = None
+        if need_dw:
             if tw is not None and SIDE_STREAM_ON:
                 with fork_side(x.device, x, dyc):  # off the critical path: overlaps the dgrad chain
                     conv_wgrad_raw(x, dyc, g, out=tw)
@@ -606,28 +613,22 @@ class _ConvBNFn(torch.autograd.Function):
             if tw is not None:
                 dw = None  # (autograd still runs the parameter's AccumulateGrad node with an undefined
                 #            gradient, so its post-accumulate hooks — gradient bucketing — fire as usual)
-        if ctx.needs_input_grad[0]:
+        if need_dx:
             acc, acc_mask, compact = link.take() if (link is not None and role == "acc") else (None, None, False)
-            src = ctx.in_src
-            complete = src is not None and role != "proj" and (
-                src.consumers == 1 or (role == "acc" and acc is not None and src.consumers == 2))
-            N, H, W, C, K, R, S, P, Q, sh, sw, ph, pw = g[:13]
-            if (role == "proj" and link is not None and not link.closed and _COMPACT_PROJ
+            bn = complete_src(acc_taken=acc is not None)
+            if (role == "proj" and link_open and _COMPACT_PROJ
                     and (R, S, sh, sw, ph, pw) == (1, 1, 2, 2, 0, 0) and H == 2 * P and W == 2 * Q):
                 # stride-2 1x1 shortcut: its gradient only reaches the even pixels — a plain GEMM over dY rows
                 gc = (N, P, Q, C, K, 1, 1, P, Q, 1, 1, 0, 0, 1, 1)
                 dx = link.park(conv_dgrad_raw(dyc, w, gc), compact=True)
             elif compact:
-                dx = conv_dgrad_raw(dyc, w, g, bn=src if complete else None, acc_sub2=acc)
+                dx = conv_dgrad_raw(dyc, w, g, bn=bn, acc_sub2=acc)
             else:
-                dx = conv_dgrad_raw(dyc, w, g, acc=acc, bn=src if complete else None, acc_mask=acc_mask)
+                dx = conv_dgrad_raw(dyc, w, g, acc=acc, bn=bn, acc_mask=acc_mask)
                 if link is not None and role == "proj":
                     dx = link.park(dx)
             ctx.in_src = None
-        if direct_bn:
-            dgamma = dbeta = None
-        return dx, dw, dgamma, dbeta, dres, None, None, None, None, None, None, None, None, None, None, None
-
+        return _grads(dx, dw, dgamma, dbeta, dres, direct_bn)
 
     @staticmethod
     def _backward_frozen(ctx, dout, x, w, gamma, yc, mbits, mean, invstd):
@@ -654,8 +655,8 @@ class _ConvBNFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = conv_dgrad_raw(dyc, w, ctx.g)
         ctx.in_src = ctx.src = ctx.res_src = None
-        return (dx, dw, dgamma if ctx.needs_input_grad[2] else None, dbeta if ctx.needs_input_grad[3] else None,
-                dres, None, None, None, None, None, None, None, None, None, None, None)
+        return _grads(dx, dw, dgamma if ctx.needs_input_grad[2] else None,
+                      dbeta if ctx.needs_input_grad[3] else None, dres=dres)
 
 
 def conv_bn(x, w, gamma, beta, rmean, rvar, stride=(1, 1), pad=(0, 0), dil=(1, 1), relu=True, residual=None,
@@ -721,11 +722,7 @@ class _ConvBNPoolFn(torch.autograd.Function):
         N, H, W, C, K, R, S, P, Q = g[:9]
         P2, Q2, pk, ps, pp = ctx.pool
         dy = dy.to(BF16).contiguous()
-        gamma_p, beta_p = ctx.bn_params
-        tg, tb = direct_grad(gamma_p), direct_grad(beta_p)
-        direct_bn = tg is not None and tb is not None
-        dgamma = tg if direct_bn else torch.empty(K, dtype=F32, device=yc.device)
-        dbeta = tb if direct_bn else torch.empty(K, dtype=F32, device=yc.device)
+        dgamma, dbeta, direct_bn = _bn_grad_targets(ctx.bn_params, K, yc.device)
         work = torch.empty((2 * 1024 + 3) * K, dtype=F32, device=yc.device)
         # s2d stem, filter gradient only: the BN + ReLU + pool backward is applied inside the stem wgrad kernel
         # (dtf_stem_wgrad_fused) from the coefficients the reduce pass leaves in work[:3K]; dyc is never formed
@@ -733,8 +730,8 @@ class _ConvBNPoolFn(torch.autograd.Function):
             64, (3, 3), (2, 2), (1, 1)) and P == 2 * P2 and Q == 2 * Q2 and W <= 128 and C == 16 and R == 4)
         dyc = None if fused else torch.empty_like(yc)
         call("dtf_maxpool_bn_bwd", ptr(dy), ptr(arg), ptr(yc), ptr(mean), ptr(invstd), ptr(gamma), N, P, Q, K, P2,
-             Q2, pk[0], pk[1], ps[0], ps[1], pp[0], pp[1], None if fused else ptr(dyc), ptr(dgamma), ptr(dbeta),
-             int(direct_bn), ptr(work), stream())
+             Q2, pk[0], pk[1], ps[0], ps[1], pp[0], pp[1], None if fused else ptr(dyc), ptr(dgamma),
+             ptr(dbeta), int(direct_bn), ptr(work), stream())
         dx = dw = None
         if fused:
             dw2 = torch.empty((K, R, S, C), dtype=F32, device=x.device)
@@ -746,9 +743,7 @@ class _ConvBNPoolFn(torch.autograd.Function):
             if tw is not None:
                 tw.add_(dw)
                 dw = None
-            if direct_bn:
-                dgamma = dbeta = None
-            return None, dw, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None, None
+            return _grads(None, dw, dgamma, dbeta, direct_bn=direct_bn)
         if ctx.needs_input_grad[0]:
             if ctx.s2d:
                 raise NotImplementedError("no input gradient through the space-to-depth stem (image input)")
@@ -763,9 +758,11 @@ class _ConvBNPoolFn(torch.autograd.Function):
                 dw = conv_wgrad_raw(x, dyc, g, out=tw)
             if tw is not None:
                 dw = None
-        if direct_bn:
-            dgamma = dbeta = None
-        return dx, dw, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None, None
+        return _grads(dx, dw, dgamma, dbeta, direct_bn=direct_bn)
+
+
+_FWD_ARGS = _ConvBNFn.forward.__code__.co_argcount - 1  # (without ctx)
+assert _ConvBNPoolFn.forward.__code__.co_argcount - 1 == _FWD_ARGS
 
 
 _S2D_IDX = {}

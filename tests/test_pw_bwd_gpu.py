@@ -222,6 +222,40 @@ def test_pw_bwd_block_gradients(cuda, monkeypatch, level):
         assert err < 1e-2, err
 
 
+def test_replaced_shortcut_gradient_is_an_error(cuda):
+    """The projection block's folded c3 hands the shortcut its raw incoming gradient, with the ReLU mask still to apply
+    recorded next to it on the shortcut's _BNSource. A tensor hook that replaces that gradient on its way to the
+    projection must not let the projection's backward take it for a masked gradient: the backward raises."""
+    from distributed_tensorflow_amd.keras import initializers
+    from distributed_tensorflow_amd.models import resnet as R
+    from distributed_tensorflow_amd.ops._util import direct_grads
+    from distributed_tensorflow_amd.variables import ParamArena
+    g = torch.Generator().manual_seed(13)
+    x = torch.randn(64, 16, 16, 64, generator=g).to(cuda).to(BF)
+    initializers.set_seed(3)
+    blocks = [R.Bottleneck(64, stride=1, project=True), R.Bottleneck(64)]
+    with torch.no_grad():
+        h = x
+        for b in blocks:
+            h = b(h, training=False)
+    arena = ParamArena([w for b in blocks for w in b.trainable_weights], device=cuda)  # noqa: F841 (owns the grads)
+    proj = blocks[0].proj
+
+    def hooked_proj(*args, **kw):
+        y = proj(*args, **kw)
+        y.register_hook(lambda grad: grad.clone())
+        return y
+
+    blocks[0].proj = hooked_proj
+    h = x.clone().requires_grad_(True)
+    for b in blocks:
+        h = b(h, training=True)
+    loss = (h.float() * torch.linspace(-1, 1, h.shape[-1], device=cuda)).square().mean()
+    with direct_grads(), pytest.raises(RuntimeError, match="shortcut's gradient was replaced or modified"):
+        loss.backward()
+    torch.cuda.synchronize()
+
+
 def test_pw_bwd_bn_stage2_block_gradients(cuda, monkeypatch):
     """Stage-2 bottlenecks (stride-2 projection block + two identity blocks, width 128): the middle block's c3 takes
     the BatchNorm-folded fused path; gradients agree with the unfused path to f32 summation order."""
