@@ -17,6 +17,8 @@
 // consecutive keys of one query per lane (one hash per 4 elements); the dK/dV kernel owns 4 queries of
 // one key and gathers the bits across its lane quad. Masking work is skipped on tiles that are entirely
 // below the causal diagonal.
+#include <initializer_list>
+
 #include "common.h"
 #include "routes.h"
 
@@ -182,6 +184,14 @@ __device__ __forceinline__ void stage_mask(float* smask, float mreg) {
   }
 }
 
+// dropped probabilities are zeroed here; the 1/keep scale is applied once, to the output row
+__device__ __forceinline__ void drop4(float (&p)[4], uint2 bits, uint32_t thr) {
+  p[0] = keep_j<0>(bits, thr) ? p[0] : 0.f;
+  p[1] = keep_j<1>(bits, thr) ? p[1] : 0.f;
+  p[2] = keep_j<2>(bits, thr) ? p[2] : 0.f;
+  p[3] = keep_j<3>(bits, thr) ? p[3] : 0.f;
+}
+
 template <int QT, bool DROP>
 __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, const int qblk, char* sk, char* sv, float* smask) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, G = lane >> 4, i = lane & 15;
@@ -193,7 +203,6 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, const int qblk,
   const bf16_t* V = a.v + b * a.ksb + h * a.ksh;
   const int off = a.Sk - a.Sq;
   const float c = a.scale * LOG2E;
-  constexpr bool drop = DROP;
   const uint32_t salt = drop_salt(a, bh);
 
   v8bf qf[QT][2];
@@ -264,20 +273,14 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, const int qblk,
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) {
           uint2 bits = make_uint2(0, 0);
-          if (drop) bits = drop_bits(a, salt, qi, (k0 >> 2) + 4 * kt + G);
+          if (DROP) bits = drop_bits(a, salt, qi, (k0 >> 2) + 4 * kt + G);
           float p[4];
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             p[r] = ex2(fmaf(s[kt][qt][r], c, -mnew));
             ls += p[r];
           }
-          // dropped probabilities are zeroed here; the 1/keep scale is applied once, to the output row
-          if (drop) {
-            p[0] = keep_j<0>(bits, a.thr) ? p[0] : 0.f;
-            p[1] = keep_j<1>(bits, a.thr) ? p[1] : 0.f;
-            p[2] = keep_j<2>(bits, a.thr) ? p[2] : 0.f;
-            p[3] = keep_j<3>(bits, a.thr) ? p[3] : 0.f;
-          }
+          if (DROP) drop4(p, bits, a.thr);
 #pragma unroll
           for (int r = 0; r < 4; ++r) s[kt][qt][r] = p[r];
         }
@@ -316,19 +319,14 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, const int qblk,
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt) {
         uint2 bits = make_uint2(0, 0);
-        if (drop) bits = drop_bits(a, salt, qi, (k0 >> 2) + 4 * kt + G);
+        if (DROP) bits = drop_bits(a, salt, qi, (k0 >> 2) + 4 * kt + G);
         float p[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           p[r] = ex2(s[kt][qt][r] - ms);
           ls += p[r];
         }
-        if (drop) {
-          p[0] = keep_j<0>(bits, a.thr) ? p[0] : 0.f;
-          p[1] = keep_j<1>(bits, a.thr) ? p[1] : 0.f;
-          p[2] = keep_j<2>(bits, a.thr) ? p[2] : 0.f;
-          p[3] = keep_j<3>(bits, a.thr) ? p[3] : 0.f;
-        }
+        if (DROP) drop4(p, bits, a.thr);
 #pragma unroll
         for (int r = 0; r < 4; ++r) s[kt][qt][r] = p[r];
       }
@@ -355,7 +353,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, const int qblk,
   for (int qt = 0; qt < QT; ++qt) {
     float L = l[qt] + __shfl_xor(l[qt], 16, 64);
     L += __shfl_xor(L, 32, 64);
-    const float inv = L > 0.f ? (drop ? a.inv_keep : 1.f) / L : 0.f;
+    const float inv = L > 0.f ? (DROP ? a.inv_keep : 1.f) / L : 0.f;
     const int qi = q0 + 16 * qt + i;
     if (qi < a.Sq) {
 #pragma unroll
@@ -966,16 +964,22 @@ __global__ void __launch_bounds__(256) attn_dq_ds_kernel(AttnArgs a, int nqt) {
   }
 }
 
+// the forward's arguments, and (dout on) what the backward adds to them: null in the forward
 AttnArgs make_args(const void* q, const void* k, const void* v, const long* qstr, const long* kstr, const void* o,
-                   const void* dout, const long* ostr, int B, int H, int Sq, int Sk, float scale, float dropout,
-                   unsigned long long seed, int causal, const float* kmask,
-                   const unsigned long long* seedctr) {
+                   const long* ostr, const float* lse, const float* kmask, int B, int H, int Sq, int Sk, float scale,
+                   float dropout, unsigned long long seed, int causal, const void* seedctr, const void* dout = nullptr,
+                   float* dvec = nullptr, void* dq = nullptr, void* dk = nullptr, void* dv = nullptr) {
   AttnArgs a{};
   a.q = (const bf16_t*)q;
   a.k = (const bf16_t*)k;
   a.v = (const bf16_t*)v;
   a.o = (bf16_t*)o;
+  a.lse = const_cast<float*>(lse);
   a.dout = (const bf16_t*)dout;
+  a.dvec = dvec;
+  a.dq = (bf16_t*)dq;
+  a.dk = (bf16_t*)dk;
+  a.dv = (bf16_t*)dv;
   a.qsb = qstr[0];
   a.qss = qstr[1];
   a.qsh = qstr[2];
@@ -995,16 +999,23 @@ AttnArgs make_args(const void* q, const void* k, const void* v, const long* qstr
   a.thr = (uint32_t)thr;
   a.inv_keep = 65536.f / (float)thr;
   a.seed = (uint32_t)(seed ^ (seed >> 32));
-  a.seedctr = dropout > 0.f ? seedctr : nullptr;
+  a.seedctr = dropout > 0.f ? (const unsigned long long*)seedctr : nullptr;
   a.nkq = (Sk + 3) / 4;
   a.causal = causal;
   a.kmask = kmask;
   return a;
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-
+// what the kernels assume of every call: head dim 64, tensors on 16 bytes and strides in multiples of 8 elements (the
+// 16-B row fragments), a dropout probability in [0, 1)
+bool attn_valid(int D, std::initializer_list<const void*> tensors, const long* qstr, const long* kstr,
+                const long* ostr, float dropout) {
+  if (D != HD) return false;
+  for (const void* p : tensors)
+    if (!aligned16(p)) return false;
+  if ((qstr[0] | qstr[1] | qstr[2] | kstr[0] | kstr[1] | kstr[2] | ostr[0] | ostr[1] | ostr[2]) & 7) return false;
+  return dropout >= 0.f && dropout < 1.f;
+}
 
 }  // namespace
 
@@ -1015,12 +1026,9 @@ DTF_API int dtf_attn_fwd(const void* q, const void* k, const void* v, const long
                          const long* ostr, float* lse, const float* kmask, int B, int H, int Sq, int Sk, int D,
                          float scale, float dropout, unsigned long long seed, int causal, const void* seedctr,
                          void* stream) {
-  if (D != HD || !aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o)) return -1;
-  if ((qstr[0] | qstr[1] | qstr[2] | kstr[0] | kstr[1] | kstr[2] | ostr[0] | ostr[1] | ostr[2]) & 7) return -1;
-  if (dropout < 0.f || dropout >= 1.f) return -1;
-  AttnArgs a = make_args(q, k, v, qstr, kstr, o, nullptr, ostr, B, H, Sq, Sk, scale, dropout, seed, causal, kmask,
-                         (const unsigned long long*)seedctr);
-  a.lse = lse;
+  if (!attn_valid(D, {q, k, v, o}, qstr, kstr, ostr, dropout)) return -1;
+  const AttnArgs a = make_args(q, k, v, qstr, kstr, o, ostr, lse, kmask, B, H, Sq, Sk, scale, dropout, seed, causal,
+                               seedctr);
   const int nqb = (Sq + 127) / 128;
   dim3 grid(pair_grid(causal, nqb), (unsigned)(B * H));
   if (a.thr < 65536u) hipLaunchKernelGGL((attn_fwd_kernel<2, true>), grid, dim3(256), 0, (hipStream_t)stream, a, nqb);
@@ -1052,19 +1060,10 @@ DTF_API int dtf_attn_bwd(const void* q, const void* k, const void* v, const long
                          const void* o, const void* dout, const long* ostr, const float* lse, float* dvec, void* dq,
                          void* dk, void* dv, const float* kmask, int B, int H, int Sq, int Sk, int D, float scale,
                          float dropout, unsigned long long seed, int causal, const void* seedctr, void* stream) {
-  if (D != HD || !aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) || !aligned16(dout) ||
-      !aligned16(dq) || !aligned16(dk) || !aligned16(dv))
-    return -1;
-  if ((qstr[0] | qstr[1] | qstr[2] | kstr[0] | kstr[1] | kstr[2] | ostr[0] | ostr[1] | ostr[2]) & 7) return -1;
-  if (dropout < 0.f || dropout >= 1.f) return -1;
+  if (!attn_valid(D, {q, k, v, o, dout, dq, dk, dv}, qstr, kstr, ostr, dropout)) return -1;
   hipStream_t st = (hipStream_t)stream;
-  AttnArgs a = make_args(q, k, v, qstr, kstr, o, dout, ostr, B, H, Sq, Sk, scale, dropout, seed, causal, kmask,
-                         (const unsigned long long*)seedctr);
-  a.lse = const_cast<float*>(lse);
-  a.dvec = dvec;
-  a.dq = (bf16_t*)dq;
-  a.dk = (bf16_t*)dk;
-  a.dv = (bf16_t*)dv;
+  const AttnArgs a = make_args(q, k, v, qstr, kstr, o, ostr, lse, kmask, B, H, Sq, Sk, scale, dropout, seed, causal,
+                               seedctr, dout, dvec, dq, dk, dv);
   const int nkb = (Sk + 127) / 128, nqb = (Sq + 127) / 128;
   // dQ first: it forms D = rowsum(dO * O) per query (dvec) that the dK/dV kernel reads
   if (causal)
@@ -1088,19 +1087,10 @@ DTF_API int dtf_attn_bwd_ds(const void* q, const void* k, const void* v, const l
                             void* dk, void* dv, const float* kmask, int B, int H, int Sq, int Sk, int D, float scale,
                             float dropout, unsigned long long seed, int causal, const void* seedctr, void* ds,
                             void* stream) {
-  if (D != HD || !aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) || !aligned16(dout) ||
-      !aligned16(dq) || !aligned16(dk) || !aligned16(dv) || !aligned16(ds))
-    return -1;
-  if ((qstr[0] | qstr[1] | qstr[2] | kstr[0] | kstr[1] | kstr[2] | ostr[0] | ostr[1] | ostr[2]) & 7) return -1;
-  if (dropout < 0.f || dropout >= 1.f) return -1;
+  if (!attn_valid(D, {q, k, v, o, dout, dq, dk, dv, ds}, qstr, kstr, ostr, dropout)) return -1;
   hipStream_t st = (hipStream_t)stream;
-  AttnArgs a = make_args(q, k, v, qstr, kstr, o, dout, ostr, B, H, Sq, Sk, scale, dropout, seed, causal, kmask,
-                         (const unsigned long long*)seedctr);
-  a.lse = const_cast<float*>(lse);
-  a.dvec = dvec;
-  a.dq = (bf16_t*)dq;
-  a.dk = (bf16_t*)dk;
-  a.dv = (bf16_t*)dv;
+  AttnArgs a = make_args(q, k, v, qstr, kstr, o, ostr, lse, kmask, B, H, Sq, Sk, scale, dropout, seed, causal, seedctr,
+                         dout, dvec, dq, dk, dv);
   a.ds = (bf16_t*)ds;
   a.dsld = (Sq + 63) / 64 * 64;
   if ((long)B * H * Sq >= (1l << 31)) return -1;

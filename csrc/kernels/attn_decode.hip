@@ -270,8 +270,6 @@ __global__ void __launch_bounds__(256) dense_skinny_kernel(const bf16_t* __restr
   }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 DTF_API int dtf_attn_decode_chunk() { return AD_CHUNK; }

@@ -122,6 +122,9 @@ __device__ __forceinline__ void fdivmod(uint32_t n, const FastDiv& f, uint32_t& 
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// the 16-byte vector accesses need their base pointers on 16 bytes
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 // Grid size for grid-stride memory-bound kernels: enough blocks to fill 256 CUs.
 static inline int stream_grid(long work_items, int block) {
   long g = (work_items + block - 1) / block;

@@ -274,8 +274,6 @@ bool table_ok(const long* th, int ntiles, int nvars, long n_param, long n_grad) 
   return true;
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 int tile_grid(int ntiles) { return ntiles < 2048 ? ntiles : 2048; }
 
 }  // namespace

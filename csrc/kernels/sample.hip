@@ -390,8 +390,6 @@ __global__ void __launch_bounds__(SM_THREADS) sample_kernel(SampleArgs a) {
   }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 // One token per row of logits [B, ld] (bf16, or f32 when f32 != 0; the first n entries of a row count), by the rule of

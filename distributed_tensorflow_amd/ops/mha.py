@@ -42,16 +42,6 @@ def uses_ds_path(causal, B, H, Sq, Sk):
     return ds_scratch_bytes(B, H, Sq, Sk) <= DS_SCRATCH_MAX_BYTES
 
 
-def _bwd(args_before_ds, B, H, Sq, Sk, dev):
-    """Run the attention backward (args: the dtf_attn_bwd argument list, causal flag at [-3])."""
-    causal = bool(args_before_ds[-3])
-    if uses_ds_path(causal, B, H, Sq, Sk):
-        ds = torch.empty(B * H * Sk * (-(-Sq // 64) * 64), dtype=BF16, device=dev)
-        call("dtf_attn_bwd_ds", *args_before_ds[:-1], ptr(ds), args_before_ds[-1])
-    else:
-        call("dtf_attn_bwd", *args_before_ds)
-
-
 def _next_seed(seed, device):
     """(host seed, device step-counter pointer or None): see ops.nn._auto_seed."""
     if seed is not None:
@@ -60,81 +50,60 @@ def _next_seed(seed, device):
     return (_seed_counter[0] * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF, rng_counter(device)
 
 
-def _strides3(b, s, h):
-    arr = (ctypes.c_long * 3)(int(b), int(s), int(h))
-    return arr, ctypes.addressof(arr)
+def _layout(ts, heads):
+    """How the kernels address ts: (B, H, Sq, Sk, D); the {batch, seq, head} strides (elements) of q (and dq), of k / v
+    (and dk / dv) and of o (and dout) as ctypes arrays; the shape of o; and the q, k, v pointers of tensors laid out as
+    ts (ts itself, or its gradients). heads > 0: one packed [B, S, 3*H*D] tensor read in place, o [B, S, H*D];
+    heads = 0: q, k, v and o [B, H, S, D]."""
+    if heads:
+        B, S, T = ts[0].shape
+        HD = T // 3
+        D = HD // heads
+        dims, strides, oshape = (B, heads, S, S, D), ((S * T, T, D),) * 2 + ((S * HD, HD, D),), (B, S, HD)
+        ptrs = lambda g: [g[0].data_ptr() + 2 * HD * j for j in range(3)]  # noqa: E731
+    else:
+        B, H, Sq, D = ts[0].shape
+        Sk = ts[1].shape[2]
+        qs = (H * Sq * D, D, Sq * D)
+        dims, strides, oshape = (B, H, Sq, Sk, D), (qs, (H * Sk * D, D, Sk * D), qs), ts[0].shape
+        ptrs = lambda g: [ptr(t) for t in g]  # noqa: E731
+    return dims, [(ctypes.c_long * 3)(*s) for s in strides], oshape, ptrs
 
 
-class _FlashPackedFn(torch.autograd.Function):
+class _FlashFn(torch.autograd.Function):
+    """ts: q, k, v [B, H, S, D] (heads = 0), or the packed projection output [B, S, 3*H*D] (heads = H)."""
+
     @staticmethod
-    def forward(ctx, qkv, kmask, heads, causal, scale, dropout, seed, ctr):
-        qkv = qkv.contiguous()
-        B, S, T = qkv.shape
-        D = T // (3 * heads)
-        HD = heads * D
-        o = torch.empty(B, S, HD, dtype=BF16, device=qkv.device)
-        lse = torch.empty(B * heads, S, dtype=F32, device=qkv.device)
-        qs, qsp = _strides3(S * T, T, D)
-        os_, osp = _strides3(S * HD, HD, D)
-        base = qkv.data_ptr()
-        call("dtf_attn_fwd", base, base + 2 * HD, base + 4 * HD, qsp, qsp, ptr(o), osp, ptr(lse), ptr(kmask), B, heads, S,
-             S, D, float(scale), float(dropout), seed, int(causal), ctr, stream())
-        ctx.save_for_backward(qkv, o, lse, kmask)
+    def forward(ctx, heads, kmask, causal, scale, dropout, seed, ctr, *ts):
+        ts = [t.contiguous() for t in ts]
+        dims, strides, oshape, ptrs = _layout(ts, heads)
+        qs, ks, os_ = map(ctypes.addressof, strides)
+        o = torch.empty(oshape, dtype=BF16, device=ts[0].device)
+        lse = torch.empty(dims[0] * dims[1], dims[2], dtype=F32, device=o.device)
+        call("dtf_attn_fwd", *ptrs(ts), qs, ks, ptr(o), os_, ptr(lse), ptr(kmask), *dims, float(scale), float(dropout),
+             seed, int(causal), ctr, stream())
+        ctx.save_for_backward(*ts, o, lse, kmask)
         ctx.cfg = (heads, causal, scale, dropout, seed, ctr)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        qkv, o, lse, kmask = ctx.saved_tensors
+        *ts, o, lse, kmask = ctx.saved_tensors
         heads, causal, scale, dropout, seed, ctr = ctx.cfg
+        dims, strides, _, ptrs = _layout(ts, heads)
+        qs, ks, os_ = map(ctypes.addressof, strides)
+        B, H, Sq, Sk, _ = dims
         do = do.to(BF16).contiguous()
-        B, S, T = qkv.shape
-        D = T // (3 * heads)
-        HD = heads * D
-        dqkv = torch.empty_like(qkv)
-        dvec = torch.empty(B * heads, S, dtype=F32, device=qkv.device)
-        qs, qsp = _strides3(S * T, T, D)
-        os_, osp = _strides3(S * HD, HD, D)
-        base, gb = qkv.data_ptr(), dqkv.data_ptr()
-        _bwd((base, base + 2 * HD, base + 4 * HD, qsp, qsp, ptr(o), ptr(do), osp, ptr(lse), ptr(dvec),
-              gb, gb + 2 * HD, gb + 4 * HD, ptr(kmask), B, heads, S, S, D, float(scale), float(dropout), seed,
-              int(causal), ctr, stream()), B, heads, S, S, qkv.device)
-        return dqkv, None, None, None, None, None, None, None
-
-
-class _FlashFn(torch.autograd.Function):
-    """Separate q, k, v tensors in [B, H, S, D] layout."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, kmask, causal, scale, dropout, seed, ctr):
-        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        B, H, Sq, D = q.shape
-        Sk = k.shape[2]
-        o = torch.empty_like(q)
-        lse = torch.empty(B * H, Sq, dtype=F32, device=q.device)
-        qs, qsp = _strides3(H * Sq * D, D, Sq * D)
-        ks, ksp = _strides3(H * Sk * D, D, Sk * D)
-        call("dtf_attn_fwd", ptr(q), ptr(k), ptr(v), qsp, ksp, ptr(o), qsp, ptr(lse), ptr(kmask), B, H, Sq, Sk, D,
-             float(scale), float(dropout), seed, int(causal), ctr, stream())
-        ctx.save_for_backward(q, k, v, o, lse, kmask)
-        ctx.cfg = (causal, scale, dropout, seed, ctr)
-        return o
-
-    @staticmethod
-    def backward(ctx, do):
-        q, k, v, o, lse, kmask = ctx.saved_tensors
-        causal, scale, dropout, seed, ctr = ctx.cfg
-        do = do.to(BF16).contiguous()
-        B, H, Sq, D = q.shape
-        Sk = k.shape[2]
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        dvec = torch.empty(B * H, Sq, dtype=F32, device=q.device)
-        qs, qsp = _strides3(H * Sq * D, D, Sq * D)
-        ks, ksp = _strides3(H * Sk * D, D, Sk * D)
-        _bwd((ptr(q), ptr(k), ptr(v), qsp, ksp, ptr(o), ptr(do), qsp, ptr(lse), ptr(dvec), ptr(dq),
-              ptr(dk), ptr(dv), ptr(kmask), B, H, Sq, Sk, D, float(scale), float(dropout), seed, int(causal),
-              ctr, stream()), B, H, Sq, Sk, q.device)
-        return dq, dk, dv, None, None, None, None, None, None
+        grads = [torch.empty_like(t) for t in ts]
+        dvec = torch.empty(B * H, Sq, dtype=F32, device=o.device)
+        args = (*ptrs(ts), qs, ks, ptr(o), ptr(do), os_, ptr(lse), ptr(dvec), *ptrs(grads), ptr(kmask), *dims,
+                float(scale), float(dropout), seed, int(causal), ctr)
+        if uses_ds_path(causal, B, H, Sq, Sk):
+            ds = torch.empty(ds_scratch_bytes(B, H, Sq, Sk) // 2, dtype=BF16, device=o.device)
+            call("dtf_attn_bwd_ds", *args, ptr(ds), stream())
+        else:
+            call("dtf_attn_bwd", *args, stream())
+        return (None,) * 7 + tuple(grads)
 
 
 def _kmask(mask, B, Sk):
@@ -152,16 +121,10 @@ def attention(q, k, v, causal=False, mask=None, scale=None, dropout=0.0, trainin
     if on_gpu(q):
         if D == 64 and k.shape[2] == v.shape[2]:
             seed, ctr = _next_seed(seed, q.device)
-            return _FlashFn.apply(q.to(BF16), k.to(BF16), v.to(BF16), _kmask(mask, B, Sk), bool(causal),
-                                  float(scale), rate, seed, ctr)
+            return _FlashFn.apply(0, _kmask(mask, B, Sk), bool(causal), float(scale), rate, seed, ctr, q.to(BF16),
+                                  k.to(BF16), v.to(BF16))
         return _composed(q, k, v, causal, mask, scale, rate)
-    s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
-    if causal:
-        m = torch.ones(Sq, Sk, dtype=torch.bool, device=q.device).tril(Sk - Sq)
-        s = s.masked_fill(~m, float("-inf"))
-    if mask is not None:
-        s = s + mask.reshape(B, 1, 1, Sk).float()
-    p = masked_row_softmax(s)  # rows with no visible key: 0, as the kernels
+    p = _reference_probs(q, k, causal, mask, scale)
     if rate:
         p = torch.nn.functional.dropout(p, rate)
     return torch.matmul(p, v.float()).to(q.dtype)
@@ -175,7 +138,7 @@ def attention_packed(qkv, heads, causal=False, mask=None, scale=None, dropout=0.
     rate = float(dropout) if (dropout and training) else 0.0
     if on_gpu(qkv) and D == 64 and qkv.dtype == BF16:
         seed, ctr = _next_seed(seed, qkv.device)
-        return _FlashPackedFn.apply(qkv, _kmask(mask, B, S), heads, bool(causal), float(scale), rate, seed, ctr)
+        return _FlashFn.apply(heads, _kmask(mask, B, S), bool(causal), float(scale), rate, seed, ctr, qkv)
     q, k, v = split_qkv(qkv, heads)
     return merge_heads(attention(q, k, v, causal, mask, scale, dropout, training))
 
@@ -198,18 +161,22 @@ def _composed(q, k, v, causal, mask, scale, rate):
     return bmm(p, v3).reshape(B, H, Sq, D)
 
 
-def reference_attention(q, k, v, causal=False, mask=None, scale=None, keep_mask=None, keep=1.0):
-    """f32 reference with an explicit dropout keep-mask (tests)."""
-    B, H, Sq, D = q.shape
-    Sk = k.shape[2]
-    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+def _reference_probs(q, k, causal, mask, scale):
+    """f32 softmax(q k^T * scale + masks) of [B, H, S, D] tensors; scale given."""
+    B, Sq, Sk = q.shape[0], q.shape[2], k.shape[2]
     s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
     if causal:
         m = torch.ones(Sq, Sk, dtype=torch.bool, device=q.device).tril(Sk - Sq)
         s = s.masked_fill(~m, float("-inf"))
     if mask is not None:
         s = s + mask.reshape(B, 1, 1, Sk).float()
-    p = masked_row_softmax(s)  # rows with no visible key: 0, as the kernels
+    return masked_row_softmax(s)  # rows with no visible key: 0, as the kernels
+
+
+def reference_attention(q, k, v, causal=False, mask=None, scale=None, keep_mask=None, keep=1.0):
+    """f32 reference with an explicit dropout keep-mask (tests)."""
+    scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    p = _reference_probs(q, k, causal, mask, scale)
     if keep_mask is not None:
         p = p * keep_mask / keep
     return torch.matmul(p, v.float())
