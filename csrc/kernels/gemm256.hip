@@ -276,7 +276,7 @@ __global__ void __launch_bounds__(NT2, 1) gemm256_kernel(GemmArgs a) {
         if (a.q8used2) a.q8used2[0] = sc;
       }
     }
-    auto q8v = [&](float f) { return fminf(fmaxf(f * q8inv, -q8fmax), q8fmax); };
+    auto q8v = [&](float f) { return fp8_sat(f * q8inv, q8fmax); };
     const bool aux_nt = a.aux_nt & 1;
     // aux_nt bit 1: the pre-activation side output is stored straight from the fragments in the main pass (8-B
     // pieces, merged in L2) instead of a second LDS-staged pass

@@ -127,6 +127,15 @@ struct GemmArgs {
   uint32_t* pixtab;
 };
 
+// Scaled value -> the finite range of an fp8 format: +-inf and everything beyond saturate to +-fmax, NaN stays NaN
+// (fminf / fmaxf alone return the bound for a NaN argument: the conversion would then store the most negative finite
+// code and a diverged run would go on training on large finite values instead of showing NaN). The NaN-propagating
+// minimum / maximum are v_minimum3_f32 / v_maximum3_f32 on gfx950: two instructions, as the fminf / fmaxf pair was
+// (a compare and select on top of that pair cost the q8 GEMM epilogues 5-6%, which quantize every value twice)
+__device__ __forceinline__ float fp8_sat(float y, float fmax) {
+  return __builtin_elementwise_minimum(__builtin_elementwise_maximum(y, -fmax), fmax);
+}
+
 // 4 floats -> 4 packed OCP fp8 bytes (fmt 0 e4m3, 1 e5m2), values already scaled and clamped
 __device__ __forceinline__ uint32_t q8pack4(int fmt, float a0, float a1, float a2, float a3) {
   int r;

@@ -16,15 +16,15 @@ namespace {
 
 __device__ __forceinline__ float fp8_max() { return 448.f; }
 
-// 8 bf16 -> 8 e4m3 bytes (x * inv, saturated to +-448)
+// 8 bf16 -> 8 e4m3 bytes (x * inv, saturated to +-448; NaN stays NaN)
 __device__ __forceinline__ uint2 quant8(const float* f, float inv) {
   uint32_t w[2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
-    float a0 = fminf(fmaxf(f[4 * h + 0] * inv, -fp8_max()), fp8_max());
-    float a1 = fminf(fmaxf(f[4 * h + 1] * inv, -fp8_max()), fp8_max());
-    float a2 = fminf(fmaxf(f[4 * h + 2] * inv, -fp8_max()), fp8_max());
-    float a3 = fminf(fmaxf(f[4 * h + 3] * inv, -fp8_max()), fp8_max());
+    float a0 = dtf::fp8_sat(f[4 * h + 0] * inv, fp8_max());
+    float a1 = dtf::fp8_sat(f[4 * h + 1] * inv, fp8_max());
+    float a2 = dtf::fp8_sat(f[4 * h + 2] * inv, fp8_max());
+    float a3 = dtf::fp8_sat(f[4 * h + 3] * inv, fp8_max());
     int r = __builtin_amdgcn_cvt_pk_fp8_f32(a0, a1, 0, false);
     r = __builtin_amdgcn_cvt_pk_fp8_f32(a2, a3, r, true);
     w[h] = (uint32_t)r;
@@ -74,7 +74,8 @@ __global__ void __launch_bounds__(256) quant_fp8_kernel(const bf16_t* __restrict
   }
 }
 
-// new scale from the amax of the previous step: scale = amax / 448 * 2^-margin  (history length 1); the amax
+// new scale from the amax of the previous step: scale = amax / 448 * 2^margin  (history length 1;
+// margin > 0 leaves headroom below 448, the callers in ops/fp8.py pass 0); the amax
 // accumulator is reset here, so the next quantize pass needs no memset
 __global__ void fp8_update_scale_kernel(float* amax, float* scale, float margin) {
   float a = amax[0];
@@ -266,7 +267,7 @@ __global__ void __launch_bounds__(256) quant_t_kernel(QtArgs a) {
     for (int h = 0; h < 4; ++h) {
       float v[4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = fminf(fmaxf(f[4 * h + j] * inv, -FMAX), FMAX);
+      for (int j = 0; j < 4; ++j) v[j] = dtf::fp8_sat(f[4 * h + j] * inv, FMAX);
       qw[h] = cvt4<FMT>(v[0], v[1], v[2], v[3]);
     }
     const long e = (long)(m0 + r) * a.N + n0 + 16 * cc;

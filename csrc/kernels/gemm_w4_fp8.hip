@@ -154,7 +154,7 @@ __device__ __forceinline__ void w8_epilogue(const GemmArgs& a, v16f (&acc)[4][BN
       if (a.q8used2) a.q8used2[0] = s8;
     }
   }
-  auto q8v = [&](float f) { return fminf(fmaxf(f * q8inv, -q8fmax), q8fmax); };
+  auto q8v = [&](float f) { return fp8_sat(f * q8inv, q8fmax); };
   constexpr int TPR = BN / 8, RPP = W4_THREADS / TPR;
   const int c8 = threadIdx.x % TPR, r0 = threadIdx.x / TPR;
   const int n = n0 + c8 * 8;
