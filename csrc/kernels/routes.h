@@ -39,6 +39,8 @@ enum LaunchCounter : int {
   LC_DENSE_SKINNY = 11, // attn_decode.hip, M <= 16 weight-streaming dense
   LC_SAMPLE = 12,       // sample.hip, the fused token sampler
   LC_ATTN_APPEND = 13,  // attention.hip, multi-token append attention over a KV cache
+  LC_DENSE_SKINNY_FUSED = 14,  // attn_decode_fused.hip, dense_skinny with LayerNorm prologue / residual / cache-store epilogue
+  LC_ATTN_DECODE_FUSED = 15,   // attn_decode_fused.hip, split-KV attention with the merge in the same launch
   LC_COUNT = 16
 };
 DTF_API long* dtf_launch_counters();  // gemm.hip

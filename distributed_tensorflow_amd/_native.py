@@ -140,6 +140,10 @@ _KERNEL_SIGS = {
     "dtf_attn_decode": [P, P, P, P, P, P, I, I, I, F, P],
     "dtf_attn_decode_chunk": [],
     "dtf_dense_skinny": [P, P, P, P, I, I, I, I, P],
+    # the fused one-token step (attn_decode_fused.hip): x, w, bias, out, M, N, K, act | gamma, beta, eps | res | k, v, lens, H, Smax | stream
+    "dtf_dense_skinny_fused": [P, P, P, P, I, I, I, I, P, P, F, P, P, P, P, I, I, P],
+    "dtf_dense_skinny_ln_max_k": [],
+    "dtf_attn_decode_fused": [P, P, P, P, P, P, P, I, I, I, F, P],
     # multi-token append attention over the cache (attention.hip): qkv, k, v, lens, out, B, S, H, Smax, scale, stream
     "dtf_attn_append": [P, P, P, P, P, I, I, I, I, F, P],
     # fused token sampler (sample.hip): logits, f32, ld, B, n, 1/T, greedy, top_k, P, r, 1/r, seed, uniform, table, out,

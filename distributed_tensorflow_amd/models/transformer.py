@@ -43,10 +43,12 @@ class _Proj(KL.Layer):
         self.bias = self.add_weight("bias", (self.units,), "zeros")
         self.built = True
 
-    def call(self, x, training=None, link=None, cache=None):
+    def call(self, x, training=None, link=None, cache=None, fused=None):
         if cache is not None:
             # inference with a KV cache runs from the bf16 shadow, also for an fp8 model (sampling during training must
             # not touch the fp8 scaling state); the one-token decode step is a weight stream (ops.dense_skinny)
+            if fused is not None:  # the fused step: ops.dense_skinny_fused's ln= / residual= / store= options
+                return decode_ops.dense_skinny_fused(x, self.kernel, self.bias, self.activation, **fused)
             if x.shape[-2] == 1:
                 return decode_ops.step_dense(x, self.kernel, self.bias, self.activation)
             return ops.dense(x, self.kernel, self.bias, act=self.activation)
@@ -56,6 +58,17 @@ class _Proj(KL.Layer):
         return ops.dense(x, self.kernel, self.bias, act=self.activation, link=link, tag_act=self.single_consumer)
 
 
+def _ln_args(layer, x):
+    """(gamma, beta, eps) of a LayerNormalization for the prologue of ops.dense_skinny_fused (built here when the
+    fused step is the layer's first use)."""
+    if not layer.built:
+        from .. import context
+        with context.device(x.device):
+            layer.build(tuple(x.shape))
+        layer.built = True
+    return layer.gamma, layer.beta, layer.epsilon
+
+
 class MultiHeadSelfAttention(KL.Layer):
     def __init__(self, hidden, heads, dropout=0.1, causal=False, fp8=False, **kw):
         super().__init__(**kw)
@@ -63,17 +76,24 @@ class MultiHeadSelfAttention(KL.Layer):
         self.qkv = _Proj(3 * hidden, fp8=fp8)
         self.out = _Proj(hidden, fp8=fp8)
 
-    def call(self, x, mask=None, training=None, link=None, cache=None, layer=None, append=False):
+    def call(self, x, mask=None, training=None, link=None, cache=None, layer=None, append=False, fused=False,
+             ln=None):
         if cache is not None:
-            return self._call_cached(x, cache, layer, append)
+            return self._call_cached(x, cache, layer, append, fused, ln)
         o = attn_ops.attention_packed(self.qkv(x, link=link), self.heads, causal=self.causal, mask=mask,
                                       dropout=self.dropout, training=training)
         return self.out(o)
 
-    def _call_cached(self, x, cache, layer, append=False):
+    def _call_cached(self, x, cache, layer, append=False, fused=False, ln=None):
         """Inference with a KV cache (ops.decode.KVCache): S > 1 is the prefill of an empty cache (the causal
         attention kernel, plus a copy of K and V into the cache), S == 1 a decode step (append, then attend);
-        append=True with S > 1 appends the chunk to a filled cache (store at lens + s, then attend_chunk)."""
+        append=True with S > 1 appends the chunk to a filled cache (store at lens + s, then attend_chunk).
+        fused=True with S == 1: x is the residual stream and ln the block's first LayerNorm; three launches
+        ([LN + QKV + cache store], [attention with its merge], [out-projection + x]) return x + attention."""
+        if fused and x.shape[1] == 1:
+            qkv = self.qkv(x, cache=cache, fused=dict(ln=_ln_args(ln, x), store=(cache, layer)))
+            o = cache.attend(layer, qkv, fused=True)
+            return self.out(o, cache=cache, fused=dict(residual=x))
         qkv = self.qkv(x, cache=cache)
         if x.shape[1] == 1:
             cache.store(layer, qkv)
@@ -177,7 +197,11 @@ class GPT2Block(KL.Layer):
         self.dropout = dropout
         object.__setattr__(self, "out_into_ln", False)  # set by GPT2: the output's first reader is a LayerNorm
 
-    def call(self, x, training=None, cache=None, layer=None, append=False):
+    def call(self, x, training=None, cache=None, layer=None, append=False, fused=False):
+        if cache is not None and fused and x.shape[1] == 1:  # the one-token step in five launches
+            x = self.att(x, training=False, cache=cache, layer=layer, fused=True, ln=self.ln1)
+            h = self.fc(x, cache=cache, fused=dict(ln=_ln_args(self.ln2, x)))
+            return self.proj(h, cache=cache, fused=dict(residual=x))
         if cache is not None:  # inference with a KV cache: no dropout, no gradient links
             x = ops.add(x, self.att(self.ln1(x), training=False, cache=cache, layer=layer, append=append))
             return ops.add(x, self.proj(self.fc(self.ln2(x), cache=cache), cache=cache))
@@ -219,22 +243,25 @@ class GPT2(Model):
         self.dropout = dropout
         self.built = True
 
-    def call(self, ids, training=None, cache=None, append=False):
+    def call(self, ids, training=None, cache=None, append=False, fused=False):
         if cache is not None:
-            return self._lm_head(self._hidden_cached(ids, cache, append), decode=ids.shape[1] == 1)
+            fused = bool(fused) and ids.shape[1] == 1  # prefill and append chunks (S > 1) are unchanged
+            return self._lm_head(self._hidden_cached(ids, cache, append, fused), decode=ids.shape[1] == 1, ln_f=fused)
         x = ops.dropout(ops.embedding(ids, self.wte, self.wpe), self.dropout, training=bool(training))
         for b in self.blocks:
             x = b(x, training=training)
         return ops.dense(self.ln_f(x), self.wte, self.pad_bias)  # tied LM head, logits over vocab_p
 
     # ---- inference with a KV cache (ops.decode)
-    def _hidden_cached(self, ids, cache, append=False):
+    def _hidden_cached(self, ids, cache, append=False, fused=False):
         """Final hidden states [B, S, hidden] of an inference forward that fills `cache`: S > 1 prefills an empty
         cache, S == 1 is a decode step at positions cache.lens, and append=True with S > 1 on a cache that is not empty
         appends the chunk at positions cache.lens + s (the caller advances lens afterwards in every case).
         With append=True the positions are clamped on the device to the position table, for S == 1 too: the pad token
         of a ragged row that is already full sits at position ctx (its output is never picked, its K/V are dropped or
-        rewritten). The default one-token step embeds at cache.lens as it is."""
+        rewritten). The default one-token step embeds at cache.lens as it is.
+        fused=True (S == 1 only): every block runs its five-launch step and the result is the residual stream before
+        ln_f, which _lm_head(ln_f=True) applies as the LM head's prologue."""
         S = ids.shape[1]
         chunk = False
         top = self.cfg["ctx"] - 1
@@ -250,9 +277,34 @@ class GPT2(Model):
             # pad positions of ragged rows may run past the position table: clamped on the device, never read back
             pos = cache.lens[:, None] + torch.arange(S, device=ids.device)[None, :]
             x = ops.embedding(ids, self.wte, self.wpe, position_ids=pos.clamp_(0, top))
+        if fused and S == 1:
+            self._check_fused(ids.shape[0], ids.device)
+            for i, b in enumerate(self.blocks):
+                x = b(x, training=False, cache=cache, layer=i, fused=True)
+            return x
         for i, b in enumerate(self.blocks):
             x = b(x, training=False, cache=cache, layer=i, append=chunk)
         return self.ln_f(x)
+
+    def _check_fused(self, batch, device):
+        """The fused one-token step has no second route: what its kernels cannot take raises here (step_dense's
+        conditions, plus the LayerNorm prologue's width cap and the cache's head dim)."""
+        if torch.device(device).type != "cuda":
+            return
+        c = self.cfg
+        hid = c["hidden"]
+        shapes = [(3 * hid, hid), (hid, hid), (4 * hid, hid), (hid, 4 * hid), (self.vocab_p, hid)]
+        if batch > 16:
+            raise ValueError(f"the fused decode step takes at most 16 rows (batch {batch})")
+        if hid % c["heads"] or hid // c["heads"] != decode_ops.HEAD_DIM:
+            raise ValueError(f"the fused decode step needs head dim {decode_ops.HEAD_DIM} (hidden {hid}, heads "
+                             f"{c['heads']})")
+        if hid % 8 or hid > decode_ops.ln_max_k():
+            raise ValueError(f"the fused decode step needs hidden % 8 == 0 and hidden <= {decode_ops.ln_max_k()} "
+                             f"(got {hid})")
+        bad = [s for s in shapes if s in decode_ops.SKINNY_EXCLUDE or s[0] % 8]
+        if bad:
+            raise ValueError(f"the fused decode step cannot run the projections {bad} (N, K) on dense_skinny")
 
     @staticmethod
     def _refuse_gpu_chunk(ids, cache, n, more):
@@ -323,7 +375,9 @@ class GPT2(Model):
                 cache.advance(valid)
             return self._lm_head(last.reshape(B, 1, -1), decode=True)[:, 0]
 
-    def _lm_head(self, h, decode=False):
+    def _lm_head(self, h, decode=False, ln_f=False):
+        if ln_f:  # the fused step: h is the residual stream, ln_f the LM head's prologue
+            return decode_ops.dense_skinny_fused(h, self.wte, self.pad_bias, ln=_ln_args(self.ln_f, h))
         if decode:
             return decode_ops.step_dense(h, self.wte, self.pad_bias)
         return ops.dense(h, self.wte, self.pad_bias)
@@ -349,7 +403,7 @@ class GPT2(Model):
 
     def generate(self, ids, max_new_tokens, *, prompt_lens=None, temperature=0.0, top_k=None, seed=None,
                  eos_token_id=None, pad_token_id=None, graph=True, cache=None, prefill_chunk=None, top_p=None,
-                 repetition_penalty=None, sampler=None):
+                 repetition_penalty=None, sampler=None, step=None):
         """Continue `ids` [B, S0] by max_new_tokens tokens with a KV cache -> int64 [B, S0 + max_new_tokens].
 
         cache: a KVCache to continue (``last_generation["cache"]`` of an earlier call, or one filled through
@@ -375,7 +429,18 @@ class GPT2(Model):
         same arguments give the same tokens on the CPU reference path of the sampler as on the GPU kernel for equal
         logits, eagerly and replayed, and for a row alone or among others at the same row index. The penalty applies
         to the tokens this call was given and produced (with cache=, not to what the cache already held). With all
-        three left at None the torch.Generator route above runs unchanged."""
+        three left at None the torch.Generator route above runs unchanged.
+
+        step="fused" runs the one-token step (captured or eager) on the fused decode kernels: five launches a layer
+        ([LN1 + QKV + cache store], [attention + merge], [out-projection + residual], [LN2 + FFN1 + GELU], [FFN2 +
+        residual]) and [ln_f + LM head], with every sampler, cache= and prefill_chunk=. A model it cannot run (batch >
+        16, hidden over the LayerNorm prologue's cap, head dim != 64) raises ValueError before anything is computed.
+        Default None: the step described above, unchanged."""
+        if step not in (None, "fused"):
+            raise ValueError(f"generate: step {step!r} (None or 'fused')")
+        step_fused = step == "fused"
+        if step_fused:
+            self._check_fused(ids.shape[0], ids.device)
         if sampler not in (None, "torch", "fused"):
             raise ValueError(f"generate: sampler {sampler!r} (None, 'torch' or 'fused')")
         if sampler == "torch" and (top_p is not None or repetition_penalty is not None):
@@ -423,8 +488,8 @@ class GPT2(Model):
                     cache = self.new_cache(B, S0 + n_new, dev, chunked=True)
                 logits = self.extend(ids, cache, plens, prefill_chunk)  # behind what the cache holds, in pieces
 
-            def step(tok):
-                lg = self._lm_head(self._hidden_cached(tok, cache), decode=True)
+            def one_token(tok):
+                lg = self._lm_head(self._hidden_cached(tok, cache, fused=step_fused), decode=True, ln_f=step_fused)
                 cache.advance(1)
                 return lg
 
@@ -441,14 +506,14 @@ class GPT2(Model):
                     tok = ops.sample_logits(logits, n=self.vocab, temperature=temperature, top_k=top_k, top_p=top_p,
                                             repetition_penalty=repetition_penalty, seed=seed, out=out, pos=pos,
                                             done=done, eos=eos_token_id, pad=int(pad))
-                    logits.copy_(step(tok[:, None])[:, 0])
+                    logits.copy_(one_token(tok[:, None])[:, 0])
                     return logits
 
             captured = None
             if graph and dev.type == "cuda":
                 from ..graphs import CapturedStep
                 # one stream only: a graph without parallel branches
-                captured = CapturedStep(fused_step if fused else step, split=False)
+                captured = CapturedStep(fused_step if fused else one_token, split=False)
             if fused:
                 for t in range(n_new):
                     (captured or fused_step)(())
@@ -459,7 +524,7 @@ class GPT2(Model):
                         tok = torch.where(done, torch.full_like(tok, int(pad)), tok)
                         done = done | (tok == int(eos_token_id))
                     out.scatter_(1, (plens + t)[:, None], tok[:, None])
-                    logits = (captured or step)(tok[:, None].contiguous())[:, 0]
+                    logits = (captured or one_token)(tok[:, None].contiguous())[:, 0]
             logits = logits.clone()
         object.__setattr__(self, "last_generation", {"cache": cache, "logits": logits, "step": captured})
         return out

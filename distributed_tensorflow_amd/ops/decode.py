@@ -1,4 +1,5 @@
-"""KV-cached decoding: the cache, single-token attention and the M <= 16 dense layer (csrc/kernels/attn_decode.hip).
+"""KV-cached decoding: the cache, single-token attention and the M <= 16 dense layer (csrc/kernels/attn_decode.hip,
+attn_decode_fused.hip).
 
 A decode step computes one token per sequence: its attention reads the keys and values of every earlier position
 (a memory-bound stream over the cache) and its projections read every weight once for at most 16 rows of activations
@@ -12,7 +13,9 @@ multi-token append kernel (``dtf_attn_append``, csrc/kernels/attention.hip) on a
 raises on a default cache (the route is opt-in per cache for now).
 
 ``dense_skinny`` is an explicit route: ``ops.dense`` / ``ops.gemm`` dispatch as before and never reach it.
-CPU tensors take the explicit f32 torch path.
+``dense_skinny_fused`` and ``KVCache.attend(fused=True)`` are the launches of the fused one-token step
+(``GPT2.generate(step="fused")``): the same kernels with LayerNorm, the residual add, the cache append and the split-KV
+merge inside them. CPU tensors take the explicit f32 torch path.
 """
 from __future__ import annotations
 
@@ -48,10 +51,12 @@ class KVCache:
         self.empty = True  # host-side: nothing stored since the last reset
         # GPU: attend_chunk with S > 1 runs the append kernel (False: it raises); the CPU path takes any S either way
         self.chunked = bool(chunked)
-        self.scratch = None
+        self.scratch = self.counters = None
         if gpu:
             self.nchunks = -(-self.capacity // decode_chunk())
             self.scratch = torch.empty(self.batch * self.heads * self.nchunks * PART, dtype=F32, device=self.device)
+            # attend(fused=True): one ticket counter per (b, h); zero here, and every call leaves them zero
+            self.counters = torch.zeros(self.batch * self.heads, dtype=torch.int32, device=self.device)
 
     def _check(self, layer, qkv, S=None):
         B, s, T = qkv.shape
@@ -80,9 +85,10 @@ class KVCache:
         self.k[layer][bi, :, pi] = x[bi, si, 1]
         self.v[layer][bi, :, pi] = x[bi, si, 2]
 
-    def attend(self, layer, qkv, scale=None):
+    def attend(self, layer, qkv, scale=None, fused=False):
         """One query row per (b, h) from qkv [B, 1, 3*H*D] over positions 0 .. min(lens[b], capacity-1) of `layer`
-        (store first: the token's own key is position lens[b]) -> [B, 1, H*D]."""
+        (store first: the token's own key is position lens[b]) -> [B, 1, H*D]. fused=True (GPU): one launch, the
+        split-KV merge done by the last block of each head; the same bits as the two-launch default."""
         self._check(layer, qkv, 1)
         B = self.batch
         HD = self.heads * self.head_dim
@@ -91,6 +97,10 @@ class KVCache:
             q = qkv if qkv.dtype == BF16 else qkv.to(BF16)
             q = q.contiguous()
             out = torch.empty(B, 1, HD, dtype=BF16, device=qkv.device)
+            if fused:
+                call("dtf_attn_decode_fused", ptr(q), ptr(self.k[layer]), ptr(self.v[layer]), ptr(self.lens), ptr(out),
+                     ptr(self.scratch), ptr(self.counters), B, self.heads, self.capacity, scale, stream(qkv.device))
+                return out
             call("dtf_attn_decode", ptr(q), ptr(self.k[layer]), ptr(self.v[layer]), ptr(self.lens), ptr(out),
                  ptr(self.scratch), B, self.heads, self.capacity, scale, stream(qkv.device))
             return out
@@ -164,6 +174,67 @@ def dense_skinny(x, w, bias=None, act=None):
         raise ValueError(f"dense_skinny: x [..., {Kd}] against w {tuple(w16.shape)}")
     out = torch.empty(M, N, dtype=BF16, device=x.device)
     call("dtf_dense_skinny", ptr(x2), ptr(w16), ptr(bias), ptr(out), M, N, Kd, a, stream(x.device))
+    return out.reshape(*x.shape[:-1], N)
+
+
+def ln_max_k():
+    """Largest K of dense_skinny_fused's LayerNorm prologue (the kernel's constant: its LDS tile)."""
+    return int(K().dtf_dense_skinny_ln_max_k())
+
+
+def dense_skinny_fused(x, w, bias=None, act=None, *, ln=None, residual=None, store=None):
+    """dense_skinny with the small neighbours of a decode step inside the same launch, each optional:
+    ln=(gamma, beta, eps): the projection reads LayerNorm(x) (x is the bf16 residual stream; K <= ln_max_k());
+    residual: out = residual + act(x w^T + bias), the projection rounded to bf16 first (the bits of ops.add after
+    dense_skinny); store=(cache, layer): w is the packed QKV projection and x holds one token per cache row; the K and
+    V thirds of the result are also written to row cache.lens[b] of `layer` (KVCache.store's rule; lens is unchanged).
+    CPU tensors take the explicit f32 composition of the same steps."""
+    a = act_code(act)
+    cache, layer = store if store is not None else (None, None)
+    if not on_gpu(x):
+        h = x
+        if ln is not None:
+            h = torch.nn.functional.layer_norm(x.float(), (x.shape[-1],), ln[0], ln[1], ln[2]).to(x.dtype)
+        y = _act_ref(torch.nn.functional.linear(h.to(w.dtype), w, bias), a)
+        if residual is not None:
+            y = residual + y
+        if cache is not None:
+            cache.store(layer, y.reshape(cache.batch, 1, -1))
+        return y
+    w16 = w if w.dtype == BF16 else bf16_shadow(w)
+    w16 = w16.contiguous()
+    x2 = x.reshape(-1, x.shape[-1])
+    x2 = (x2 if x2.dtype == BF16 else x2.to(BF16)).contiguous()
+    if bias is not None and (bias.dtype != F32 or not bias.is_contiguous()):
+        bias = bias.float().contiguous()
+    M, Kd = x2.shape
+    N = w16.shape[0]
+    if w16.shape[1] != Kd:
+        raise ValueError(f"dense_skinny_fused: x [..., {Kd}] against w {tuple(w16.shape)}")
+    gamma = beta = None
+    eps = 0.0
+    if ln is not None:
+        gamma, beta = (t.detach().float().contiguous() for t in ln[:2])
+        eps = float(ln[2])
+        if gamma.numel() != Kd or beta.numel() != Kd or Kd > ln_max_k():
+            raise ValueError(f"dense_skinny_fused: LayerNorm of width {Kd} (gamma {gamma.numel()}, beta {beta.numel()}, "
+                             f"at most {ln_max_k()})")
+    if residual is not None:
+        if residual.numel() != M * N:
+            raise ValueError(f"dense_skinny_fused: residual {tuple(residual.shape)} against an output [{M}, {N}]")
+        residual = (residual if residual.dtype == BF16 else residual.to(BF16)).contiguous()
+    kc = vc = lens = None
+    H = Smax = 0
+    if cache is not None:
+        if (not on_gpu(cache.k) or cache.batch != M or N != 3 * cache.heads * HEAD_DIM or cache.head_dim != HEAD_DIM
+                or not 0 <= layer < cache.layers):
+            raise ValueError(f"dense_skinny_fused: an output [{M}, {N}] / layer {layer} does not fit the cache (batch "
+                             f"{cache.batch}, heads {cache.heads}, head dim {cache.head_dim}, layers {cache.layers})")
+        kc, vc, lens, H, Smax = cache.k[layer], cache.v[layer], cache.lens, cache.heads, cache.capacity
+        cache.empty = False
+    out = torch.empty(M, N, dtype=BF16, device=x.device)
+    call("dtf_dense_skinny_fused", ptr(x2), ptr(w16), ptr(bias), ptr(out), M, N, Kd, a, ptr(gamma), ptr(beta), eps,
+         ptr(residual), ptr(kc), ptr(vc), ptr(lens), H, Smax, stream(x.device))
     return out.reshape(*x.shape[:-1], N)
 
 

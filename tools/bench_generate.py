@@ -17,6 +17,10 @@ min..max spread over the rounds is reported; times are host clocks around work t
  5. (--sections 5) continuing a filled cache: N in {16, 64, 256} new tokens behind L in {1, 256, 768} cached ones at
     B in {1, 8}: token by token (extend(chunk=1), and the captured one-token step replayed N times) against one chunked
     extend on a chunked=True cache; and dtf_attn_append alone with the K/V bytes it must read over its time.
+ 6. (--sections 6) each launch of the fused one-token step (generate(step="fused")) alone against the calls it replaces,
+    on the GPT-2-medium shapes at M = 1, 8, 16 (weights rotating through HBM as in section 3, every arm a replayed
+    graph). Section 1 carries the whole step: "step captured, fused" next to "step captured", alternating inside each
+    round, with the ratio fused / unfused per round.
 """
 import argparse
 import os
@@ -106,6 +110,16 @@ def section_generate(dev, rounds):
                     cap(tok)
                 assert cap.captured
 
+                def step_fused(t):
+                    lg = model(t, training=False, cache=cache, fused=True)
+                    cache.advance(1)
+                    return lg
+
+                capf = CapturedStep(step_fused, split=False)
+                for _ in range(4):
+                    capf(tok)
+                assert capf.captured
+
                 def run_steps(f):
                     def go():
                         cache.lens.fill_(S0)  # stay at context S0 .. S0 + steps
@@ -113,7 +127,7 @@ def section_generate(dev, rounds):
                             f(tok)
                     return go
 
-                r = rounds_of({"eager": run_steps(step), "captured": run_steps(cap),
+                r = rounds_of({"eager": run_steps(step), "captured": run_steps(cap), "fused": run_steps(capf),
                                "recompute": lambda: model(ids, training=False)}, rounds, 1)
                 pf = rounds_of({"prefill": prefill}, rounds, 1)["prefill"]
                 eager = [t / steps for t in r["eager"]]
@@ -122,11 +136,71 @@ def section_generate(dev, rounds):
                 say(f"B={B} context {S0}..{S0 + steps} (capacity {cache.capacity}): prefill({S0}) {fmt(pf)}")
                 say(f"    step eager    {fmt(eager)} /token")
                 say(f"    step captured {fmt(capt)} /token")
+                fus = [t / steps for t in r["fused"]]
+                rat = [f / c for f, c in zip(fus, capt)]   # per round: the arms alternate
+                say(f"    step captured, fused {fmt(fus)} /token  -> fused / unfused = {statistics.median(rat):.3f} "
+                    f"({min(rat):.3f}..{max(rat):.3f}); the unfused step's rounds spread "
+                    f"{min(capt) / statistics.median(capt):.3f}..{max(capt) / statistics.median(capt):.3f} of their median")
                 say(f"    recompute model(ids[{B},{L}]) {fmt(r['recompute'])} /token  -> captured step is "
                     f"{ratio:.1f}x faster")
-                del cap, cache
+                del cap, capf, cache
         del model
     torch.cuda.empty_cache()
+
+
+def section_fused_parts(dev, rounds):
+    say("== 6. each fused launch alone vs the calls it replaces (GPT-2-medium shapes, H = 16, cache capacity 1024 at "
+        "length 512; us per layer-call inside a replayed graph, weights rotating through HBM)")
+    H, L = 16, 1024
+    parts = (("LN1+QKV+store", 1024, 3072, None, True, False, True),
+             ("out-proj+residual", 1024, 1024, None, False, True, False),
+             ("LN2+FFN1+GELU", 1024, 4096, "gelu", True, False, False),
+             ("FFN2+residual", 4096, 1024, None, False, True, False),
+             ("ln_f+LM head", 1024, 50304, None, True, False, False))
+    with torch.no_grad():
+        for M in (1, 8, 16):
+            cache = ops.KVCache(1, M, H, L, dev)
+            cache.k.normal_()
+            cache.v.normal_()
+            cache.lens.fill_(L // 2)
+            for name, K, N, act, ln, res, store in parts:
+                copies = max(2, min(64, (512 << 20) // (N * K * 2)))
+                ws = [torch.randn(N, K, device=dev) * 0.02 for _ in range(copies)]
+                for w in ws:
+                    ops._util.bf16_shadow(w)
+                bias = torch.zeros(N, device=dev)
+                gamma, beta = torch.ones(K, device=dev), torch.zeros(K, device=dev)
+                x = torch.randn(M, 1, K, device=dev).to(torch.bfloat16)
+                r0 = torch.randn(M, 1, N, device=dev).to(torch.bfloat16)
+
+                def unfused():
+                    for w in ws:
+                        y = ops.dense_skinny(ops.layer_norm(x, gamma, beta, 1e-5) if ln else x, w, bias, act)
+                        if store:
+                            cache.store(0, y)
+                        if res:
+                            ops.add(r0, y)
+
+                def fused():
+                    for w in ws:
+                        ops.dense_skinny_fused(x, w, bias, act, ln=(gamma, beta, 1e-5) if ln else None,
+                                               residual=r0 if res else None, store=(cache, 0) if store else None)
+
+                r = rounds_of({"unfused": graph_of(unfused), "fused": graph_of(fused)}, rounds, 10)
+                un = [t / copies for t in r["unfused"]]
+                fu = [t / copies for t in r["fused"]]
+                say(f"M={M:2d} {name:18s} {K:5d}->{N:5d}: replaced calls {fmt(un, 1e6, 'us')}   fused "
+                    f"{fmt(fu, 1e6, 'us')}   fused / unfused = {statistics.median(fu) / statistics.median(un):.2f}")
+                del ws
+                torch.cuda.empty_cache()
+            qkv = torch.randn(M, 1, 3 * H * 64, device=dev).to(torch.bfloat16)
+            cache.lens.fill_(L - 1)
+            r = rounds_of({"two": graph_of(lambda: [cache.attend(0, qkv) for _ in range(16)]),
+                           "one": graph_of(lambda: [cache.attend(0, qkv, fused=True) for _ in range(16)])}, rounds, 10)
+            two, one = [t / 16 for t in r["two"]], [t / 16 for t in r["one"]]
+            say(f"M={M:2d} attention+merge    L = {L}, one layer: two launches {fmt(two, 1e6, 'us')}   one launch "
+                f"{fmt(one, 1e6, 'us')}   fused / unfused = {statistics.median(one) / statistics.median(two):.2f}")
+            del cache
 
 
 def section_attention(dev, rounds):
@@ -358,6 +432,8 @@ def main():
         section_sampler(dev, a.rounds)
     if "5" in sec:
         section_append(dev, a.rounds)
+    if "6" in sec:
+        section_fused_parts(dev, a.rounds)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "a" if a.append else "w") as f:
         f.write("\n".join(LINES) + "\n")
