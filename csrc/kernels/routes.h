@@ -41,7 +41,8 @@ enum LaunchCounter : int {
   LC_ATTN_APPEND = 13,  // attention.hip, multi-token append attention over a KV cache
   LC_DENSE_SKINNY_FUSED = 14,  // attn_decode_fused.hip, dense_skinny with LayerNorm prologue / residual / cache-store epilogue
   LC_ATTN_DECODE_FUSED = 15,   // attn_decode_fused.hip, split-KV attention with the merge in the same launch
-  LC_COUNT = 16
+  LC_DENSE_WIDE = 16,          // dense_wide.hip, M <= 64 weight-streaming dense
+  LC_COUNT = 17
 };
 DTF_API long* dtf_launch_counters();  // gemm.hip
 inline void count_launch(int c) { dtf_launch_counters()[c]++; }

@@ -144,6 +144,9 @@ _KERNEL_SIGS = {
     "dtf_dense_skinny_fused": [P, P, P, P, I, I, I, I, P, P, F, P, P, P, P, I, I, P],
     "dtf_dense_skinny_ln_max_k": [],
     "dtf_attn_decode_fused": [P, P, P, P, P, P, P, I, I, I, F, P],
+    # the M <= 64 weight stream (dense_wide.hip): x, w, bias, out, M, N, K, act, [variant,] stream
+    "dtf_dense_wide": [P, P, P, P, I, I, I, I, P],
+    "dtf_dense_wide_variant": [P, P, P, P, I, I, I, I, I, P],
     # multi-token append attention over the cache (attention.hip): qkv, k, v, lens, out, B, S, H, Smax, scale, stream
     "dtf_attn_append": [P, P, P, P, P, I, I, I, I, F, P],
     # fused token sampler (sample.hip): logits, f32, ld, B, n, 1/T, greedy, top_k, P, r, 1/r, seed, uniform, table, out,

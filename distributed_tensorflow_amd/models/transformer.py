@@ -43,14 +43,14 @@ class _Proj(KL.Layer):
         self.bias = self.add_weight("bias", (self.units,), "zeros")
         self.built = True
 
-    def call(self, x, training=None, link=None, cache=None, fused=None):
+    def call(self, x, training=None, link=None, cache=None, fused=None, wide=False):
         if cache is not None:
             # inference with a KV cache runs from the bf16 shadow, also for an fp8 model (sampling during training must
             # not touch the fp8 scaling state); the one-token decode step is a weight stream (ops.dense_skinny)
             if fused is not None:  # the fused step: ops.dense_skinny_fused's ln= / residual= / store= options
                 return decode_ops.dense_skinny_fused(x, self.kernel, self.bias, self.activation, **fused)
             if x.shape[-2] == 1:
-                return decode_ops.step_dense(x, self.kernel, self.bias, self.activation)
+                return decode_ops.step_dense(x, self.kernel, self.bias, self.activation, wide=wide)
             return ops.dense(x, self.kernel, self.bias, act=self.activation)
         if self.fp8 and x.is_cuda:
             from ..ops.fp8 import dense_fp8
@@ -77,24 +77,25 @@ class MultiHeadSelfAttention(KL.Layer):
         self.out = _Proj(hidden, fp8=fp8)
 
     def call(self, x, mask=None, training=None, link=None, cache=None, layer=None, append=False, fused=False,
-             ln=None):
+             ln=None, wide=False):
         if cache is not None:
-            return self._call_cached(x, cache, layer, append, fused, ln)
+            return self._call_cached(x, cache, layer, append, fused, ln, wide)
         o = attn_ops.attention_packed(self.qkv(x, link=link), self.heads, causal=self.causal, mask=mask,
                                       dropout=self.dropout, training=training)
         return self.out(o)
 
-    def _call_cached(self, x, cache, layer, append=False, fused=False, ln=None):
+    def _call_cached(self, x, cache, layer, append=False, fused=False, ln=None, wide=False):
         """Inference with a KV cache (ops.decode.KVCache): S > 1 is the prefill of an empty cache (the causal
         attention kernel, plus a copy of K and V into the cache), S == 1 a decode step (append, then attend);
         append=True with S > 1 appends the chunk to a filled cache (store at lens + s, then attend_chunk).
         fused=True with S == 1: x is the residual stream and ln the block's first LayerNorm; three launches
-        ([LN + QKV + cache store], [attention with its merge], [out-projection + x]) return x + attention."""
+        ([LN + QKV + cache store], [attention with its merge], [out-projection + x]) return x + attention.
+        wide=True: the two projections of a decode step with 17 to 64 rows run ops.dense_wide (step_dense)."""
         if fused and x.shape[1] == 1:
             qkv = self.qkv(x, cache=cache, fused=dict(ln=_ln_args(ln, x), store=(cache, layer)))
             o = cache.attend(layer, qkv, fused=True)
             return self.out(o, cache=cache, fused=dict(residual=x))
-        qkv = self.qkv(x, cache=cache)
+        qkv = self.qkv(x, cache=cache, wide=wide)
         if x.shape[1] == 1:
             cache.store(layer, qkv)
             o = cache.attend(layer, qkv)
@@ -104,7 +105,7 @@ class MultiHeadSelfAttention(KL.Layer):
         else:
             o = attn_ops.attention_packed(qkv, self.heads, causal=True, dropout=0.0, training=False)
             cache.store(layer, qkv)
-        return self.out(o, cache=cache)
+        return self.out(o, cache=cache, wide=wide)
 
 
 class BertLayer(KL.Layer):
@@ -197,14 +198,14 @@ class GPT2Block(KL.Layer):
         self.dropout = dropout
         object.__setattr__(self, "out_into_ln", False)  # set by GPT2: the output's first reader is a LayerNorm
 
-    def call(self, x, training=None, cache=None, layer=None, append=False, fused=False):
+    def call(self, x, training=None, cache=None, layer=None, append=False, fused=False, wide=False):
         if cache is not None and fused and x.shape[1] == 1:  # the one-token step in five launches
             x = self.att(x, training=False, cache=cache, layer=layer, fused=True, ln=self.ln1)
             h = self.fc(x, cache=cache, fused=dict(ln=_ln_args(self.ln2, x)))
             return self.proj(h, cache=cache, fused=dict(residual=x))
         if cache is not None:  # inference with a KV cache: no dropout, no gradient links
-            x = ops.add(x, self.att(self.ln1(x), training=False, cache=cache, layer=layer, append=append))
-            return ops.add(x, self.proj(self.fc(self.ln2(x), cache=cache), cache=cache))
+            x = ops.add(x, self.att(self.ln1(x), training=False, cache=cache, layer=layer, append=append, wide=wide))
+            return ops.add(x, self.proj(self.fc(self.ln2(x), cache=cache, wide=wide), cache=cache, wide=wide))
         # the residual gradient of each half-block's input joins its LayerNorm's backward (ResidualGradLink)
         l1, l2 = (ResidualGradLink(), ResidualGradLink()) if (LN_LINK and training and x.is_cuda
                                                               and torch.is_grad_enabled()) else (None, None)
@@ -243,17 +244,19 @@ class GPT2(Model):
         self.dropout = dropout
         self.built = True
 
-    def call(self, ids, training=None, cache=None, append=False, fused=False):
+    def call(self, ids, training=None, cache=None, append=False, fused=False, wide=False):
         if cache is not None:
-            fused = bool(fused) and ids.shape[1] == 1  # prefill and append chunks (S > 1) are unchanged
-            return self._lm_head(self._hidden_cached(ids, cache, append, fused), decode=ids.shape[1] == 1, ln_f=fused)
+            one = ids.shape[1] == 1  # prefill and append chunks (S > 1) are unchanged by fused= and wide=
+            fused, wide = bool(fused) and one, bool(wide) and one
+            h = self._hidden_cached(ids, cache, append, fused, wide)
+            return self._lm_head(h, decode=one, ln_f=fused, wide=wide)
         x = ops.dropout(ops.embedding(ids, self.wte, self.wpe), self.dropout, training=bool(training))
         for b in self.blocks:
             x = b(x, training=training)
         return ops.dense(self.ln_f(x), self.wte, self.pad_bias)  # tied LM head, logits over vocab_p
 
     # ---- inference with a KV cache (ops.decode)
-    def _hidden_cached(self, ids, cache, append=False, fused=False):
+    def _hidden_cached(self, ids, cache, append=False, fused=False, wide=False):
         """Final hidden states [B, S, hidden] of an inference forward that fills `cache`: S > 1 prefills an empty
         cache, S == 1 is a decode step at positions cache.lens, and append=True with S > 1 on a cache that is not empty
         appends the chunk at positions cache.lens + s (the caller advances lens afterwards in every case).
@@ -261,7 +264,8 @@ class GPT2(Model):
         of a ragged row that is already full sits at position ctx (its output is never picked, its K/V are dropped or
         rewritten). The default one-token step embeds at cache.lens as it is.
         fused=True (S == 1 only): every block runs its five-launch step and the result is the residual stream before
-        ln_f, which _lm_head(ln_f=True) applies as the LM head's prologue."""
+        ln_f, which _lm_head(ln_f=True) applies as the LM head's prologue.
+        wide=True (S == 1 only): the default step with ops.dense_wide for the projections at 17 to 64 rows."""
         S = ids.shape[1]
         chunk = False
         top = self.cfg["ctx"] - 1
@@ -282,8 +286,11 @@ class GPT2(Model):
             for i, b in enumerate(self.blocks):
                 x = b(x, training=False, cache=cache, layer=i, fused=True)
             return x
+        wide = bool(wide) and S == 1
+        if wide:
+            self._check_wide(ids.shape[0], ids.device)
         for i, b in enumerate(self.blocks):
-            x = b(x, training=False, cache=cache, layer=i, append=chunk)
+            x = b(x, training=False, cache=cache, layer=i, append=chunk, wide=wide)
         return self.ln_f(x)
 
     def _check_fused(self, batch, device):
@@ -305,6 +312,19 @@ class GPT2(Model):
         bad = [s for s in shapes if s in decode_ops.SKINNY_EXCLUDE or s[0] % 8]
         if bad:
             raise ValueError(f"the fused decode step cannot run the projections {bad} (N, K) on dense_skinny")
+
+    def _check_wide(self, batch, device):
+        """The wide one-token step: more rows than ops.dense_wide takes, or (past dense_skinny's 16 rows) a projection
+        it cannot run, raises here; a shape in WIDE_EXCLUDE is one it was measured not to win and stays on ops.dense."""
+        if torch.device(device).type != "cuda":
+            return
+        if batch > decode_ops.WIDE_MAX_ROWS:
+            raise ValueError(f"the wide decode step takes at most {decode_ops.WIDE_MAX_ROWS} rows (batch {batch})")
+        hid = self.cfg["hidden"]
+        shapes = [(3 * hid, hid), (hid, hid), (4 * hid, hid), (hid, 4 * hid), (self.vocab_p, hid)]
+        bad = [s for s in shapes if s[0] % 8 or s[1] % 8]
+        if batch > 16 and bad:
+            raise ValueError(f"the wide decode step cannot run the projections {bad} (N, K) on dense_wide")
 
     @staticmethod
     def _refuse_gpu_chunk(ids, cache, n, more):
@@ -375,11 +395,11 @@ class GPT2(Model):
                 cache.advance(valid)
             return self._lm_head(last.reshape(B, 1, -1), decode=True)[:, 0]
 
-    def _lm_head(self, h, decode=False, ln_f=False):
+    def _lm_head(self, h, decode=False, ln_f=False, wide=False):
         if ln_f:  # the fused step: h is the residual stream, ln_f the LM head's prologue
             return decode_ops.dense_skinny_fused(h, self.wte, self.pad_bias, ln=_ln_args(self.ln_f, h))
         if decode:
-            return decode_ops.step_dense(h, self.wte, self.pad_bias)
+            return decode_ops.step_dense(h, self.wte, self.pad_bias, wide=wide)
         return ops.dense(h, self.wte, self.pad_bias)
 
     def new_cache(self, batch, capacity, device, chunked=False):
@@ -435,12 +455,17 @@ class GPT2(Model):
         ([LN1 + QKV + cache store], [attention + merge], [out-projection + residual], [LN2 + FFN1 + GELU], [FFN2 +
         residual]) and [ln_f + LM head], with every sampler, cache= and prefill_chunk=. A model it cannot run (batch >
         16, hidden over the LayerNorm prologue's cap, head dim != 64) raises ValueError before anything is computed.
-        Default None: the step described above, unchanged."""
-        if step not in (None, "fused"):
-            raise ValueError(f"generate: step {step!r} (None or 'fused')")
-        step_fused = step == "fused"
+        step="wide" runs the projections of the one-token step (four a layer and the LM head) on ``ops.dense_wide``, the
+        weight stream for 17 to 64 rows, when 16 < batch <= 64; up to 16 rows it is the default step, bit for bit.
+        Batch > 64 or a hidden size that is no multiple of 8 raises ValueError before anything is computed.
+        Default None: the step described above, unchanged (past 16 rows its projections run ``ops.dense``)."""
+        if step not in (None, "fused", "wide"):
+            raise ValueError(f"generate: step {step!r} (None, 'fused' or 'wide')")
+        step_fused, step_wide = step == "fused", step == "wide"
         if step_fused:
             self._check_fused(ids.shape[0], ids.device)
+        if step_wide:
+            self._check_wide(ids.shape[0], ids.device)
         if sampler not in (None, "torch", "fused"):
             raise ValueError(f"generate: sampler {sampler!r} (None, 'torch' or 'fused')")
         if sampler == "torch" and (top_p is not None or repetition_penalty is not None):
@@ -489,7 +514,8 @@ class GPT2(Model):
                 logits = self.extend(ids, cache, plens, prefill_chunk)  # behind what the cache holds, in pieces
 
             def one_token(tok):
-                lg = self._lm_head(self._hidden_cached(tok, cache, fused=step_fused), decode=True, ln_f=step_fused)
+                lg = self._lm_head(self._hidden_cached(tok, cache, fused=step_fused, wide=step_wide), decode=True,
+                                   ln_f=step_fused, wide=step_wide)
                 cache.advance(1)
                 return lg
 

@@ -15,7 +15,9 @@ raises on a default cache (the route is opt-in per cache for now).
 ``dense_skinny`` is an explicit route: ``ops.dense`` / ``ops.gemm`` dispatch as before and never reach it.
 ``dense_skinny_fused`` and ``KVCache.attend(fused=True)`` are the launches of the fused one-token step
 (``GPT2.generate(step="fused")``): the same kernels with LayerNorm, the residual add, the cache append and the split-KV
-merge inside them. CPU tensors take the explicit f32 torch path.
+merge inside them. ``dense_wide`` (csrc/kernels/dense_wide.hip) is the weight stream for up to 64 rows, the projections
+of the opt-in wide step (``GPT2.generate(step="wide")``) at 17 to 64 sequences. CPU tensors take the explicit f32 torch
+path.
 """
 from __future__ import annotations
 
@@ -177,6 +179,38 @@ def dense_skinny(x, w, bias=None, act=None):
     return out.reshape(*x.shape[:-1], N)
 
 
+WIDE_MAX_ROWS = 64
+WIDE_VARIANTS = ((8, 1), (16, 1), (16, 2), (16, 4))  # (R, T) of dense_wide_kernel, in the order of `variant`
+
+
+def dense_wide(x, w, bias=None, act=None, *, variant=None):
+    """act(x @ w^T + bias) for at most 64 rows of x (all leading axes together): the weight-streaming kernel of a
+    batched decode step past dense_skinny's 16 rows (csrc/kernels/dense_wide.hip). Arguments as dense_skinny's.
+    variant: index into WIDE_VARIANTS to run that (rows per group, groups per block) instead of the measured choice
+    (tools/bench_generate.py times them all)."""
+    a = act_code(act)
+    if not on_gpu(x):
+        y = torch.nn.functional.linear(x.to(w.dtype), w, bias)
+        return _act_ref(y, a)
+    w16 = w if w.dtype == BF16 else bf16_shadow(w)
+    w16 = w16.contiguous()
+    x2 = x.reshape(-1, x.shape[-1])
+    x2 = (x2 if x2.dtype == BF16 else x2.to(BF16)).contiguous()
+    if bias is not None and (bias.dtype != F32 or not bias.is_contiguous()):
+        bias = bias.float().contiguous()
+    M, Kd = x2.shape
+    N = w16.shape[0]
+    if w16.shape[1] != Kd:
+        raise ValueError(f"dense_wide: x [..., {Kd}] against w {tuple(w16.shape)}")
+    out = torch.empty(M, N, dtype=BF16, device=x.device)
+    if variant is None:
+        call("dtf_dense_wide", ptr(x2), ptr(w16), ptr(bias), ptr(out), M, N, Kd, a, stream(x.device))
+    else:
+        call("dtf_dense_wide_variant", ptr(x2), ptr(w16), ptr(bias), ptr(out), M, N, Kd, a, int(variant),
+             stream(x.device))
+    return out.reshape(*x.shape[:-1], N)
+
+
 def ln_max_k():
     """Largest K of dense_skinny_fused's LayerNorm prologue (the kernel's constant: its LDS tile)."""
     return int(K().dtf_dense_skinny_ln_max_k())
@@ -241,13 +275,19 @@ def dense_skinny_fused(x, w, bias=None, act=None, *, ln=None, residual=None, sto
 # (N, K) of projections that the decode step keeps on ops.dense because dense_skinny measured slower there
 # (tools/bench_generate.py, profiles/generate_decode.txt)
 SKINNY_EXCLUDE = frozenset()
+# the same for dense_wide inside the wide step (generate(step="wide")) at 17 to 64 rows. The GPT-2 LM head
+# 1024 -> 50304: 1.08x faster than ops.dense at M = 17, but 0.9x / 0.8x / 0.7x at M = 32 / 48 / 64 (section 7)
+WIDE_EXCLUDE = frozenset({(50304, 1024)})
 
 
-def step_dense(x, w, bias=None, act=None):
-    """A projection of the one-token decode step: dense_skinny from the bf16 shadow of w wherever it applies."""
+def step_dense(x, w, bias=None, act=None, wide=False):
+    """A projection of the one-token decode step: dense_skinny from the bf16 shadow of w wherever it applies.
+    wide=True (the opt-in wide step): with 17 to 64 rows dense_wide instead of ops.dense; up to 16 rows unchanged."""
     if on_gpu(x):
         M = x.numel() // x.shape[-1]
         N, Kd = w.shape
         if M <= 16 and N % 8 == 0 and Kd % 8 == 0 and (N, Kd) not in SKINNY_EXCLUDE:
             return dense_skinny(x, w, bias, act)
+        if wide and 16 < M <= WIDE_MAX_ROWS and N % 8 == 0 and Kd % 8 == 0 and (N, Kd) not in WIDE_EXCLUDE:
+            return dense_wide(x, w, bias, act)
     return dense(x, w, bias, act=act)

@@ -21,6 +21,9 @@ min..max spread over the rounds is reported; times are host clocks around work t
     on the GPT-2-medium shapes at M = 1, 8, 16 (weights rotating through HBM as in section 3, every arm a replayed
     graph). Section 1 carries the whole step: "step captured, fused" next to "step captured", alternating inside each
     round, with the ratio fused / unfused per round.
+ 7. (--sections 7) past 16 rows: ops.dense_wide, and each (R, T) variant of its kernel, against ops.dense at M = 17,
+    32, 48, 64 on the same shapes (as section 3), and the captured one-token step at B = 32 and 64, context ~350 and
+    ~1000, default against wide=True (generate(step="wide")).
 """
 import argparse
 import os
@@ -264,6 +267,87 @@ def section_dense(dev, rounds):
         + (", ".join(f"{k}->{n} at M={m}" for k, n, m in slower) if slower else "none"))
 
 
+def section_wide(dev, rounds):
+    say("== 7. ops.dense_wide vs ops.dense at 17 to 64 rows, GPT-2-medium projections (K -> N), weights rotating "
+        "through HBM; every (R, T) variant of the kernel, `wide` is the one dtf_dense_wide launches")
+    from distributed_tensorflow_amd.ops.decode import WIDE_VARIANTS, dense_wide
+    not_faster = []
+    with torch.no_grad():
+        for K, N in ((1024, 3072), (1024, 1024), (1024, 4096), (4096, 1024), (1024, 50304)):
+            wbytes = N * K * 2
+            copies = max(2, min(64, (512 << 20) // wbytes))
+            ws = [torch.randn(N, K, device=dev) * 0.02 for _ in range(copies)]
+            bias = torch.zeros(N, device=dev)
+            for w in ws:
+                ops._util.bf16_shadow(w)
+            for M in (17, 32, 48, 64):
+                x = torch.randn(M, K, device=dev).to(torch.bfloat16)
+
+                def arm(variant):
+                    return graph_of(lambda: [dense_wide(x, w, bias, variant=variant) for w in ws])
+
+                arms = {"dense": graph_of(lambda: [ops.dense(x, w, bias) for w in ws]), "wide": arm(None)}
+                arms.update({f"R{r}T{t}": arm(v) for v, (r, t) in enumerate(WIDE_VARIANTS)})
+                res = {k: [t / copies for t in ts] for k, ts in rounds_of(arms, rounds, 10).items()}
+                de, wi = res["dense"], res["wide"]
+                bw = wbytes / statistics.median(wi)
+                # faster only by more than the baseline's own spread: the slowest wide round under the fastest dense one
+                verdict = "" if max(wi) < min(de) else "   <-- NOT FASTER than ops.dense beyond the spread"
+                if verdict:
+                    not_faster.append((K, N, M))
+                say(f"{K:5d}->{N:5d} M={M:2d} ({copies:2d} copies): wide {fmt(wi, 1e6, 'us')} "
+                    f"[{bw / 1e12:.2f} TB/s, {100 * bw / COPY_BW:.0f}% of copy bw]   dense {fmt(de, 1e6, 'us')}   "
+                    f"x{statistics.median(de) / statistics.median(wi):.2f}{verdict}")
+                say("        " + "   ".join(f"({r:2d},{t}) {fmt(res[f'R{r}T{t}'], 1e6, 'us')}" for r, t in WIDE_VARIANTS))
+                del arms
+            del ws
+            torch.cuda.empty_cache()
+    say("shapes where dense_wide is not faster than ops.dense (these belong in ops.decode.WIDE_EXCLUDE): "
+        + (", ".join(f"{k}->{n} at M={m}" for k, n, m in not_faster) if not_faster else "none"))
+    say("per token: the captured one-token step of GPT-2-medium, default (projections on ops.dense past 16 rows) "
+        "against wide=True, alternating inside each round")
+    with context.device(dev), torch.no_grad():
+        model = gpt2_medium(dropout=0.0)
+        for B in (32, 64):
+            for L in (384, 1024):
+                S0, steps = L - 32, 24
+                torch.manual_seed(B * 10000 + L)
+                tok = torch.randint(0, model.vocab, (B, 1), device=dev)
+                cache = model.new_cache(B, L, dev)
+                cache.k.normal_()
+                cache.v.normal_()
+                cache.empty = False  # "filled": only lens says how far
+                cache.lens.fill_(S0)
+
+                def stepper(wide):
+                    def step(t):
+                        lg = model(t, training=False, cache=cache, wide=wide)
+                        cache.advance(1)
+                        return lg
+                    cap = CapturedStep(step, split=False)
+                    for _ in range(4):
+                        cap(tok)
+                    assert cap.captured
+
+                    def go():
+                        cache.lens.fill_(S0)  # stay at context S0 .. S0 + steps
+                        for _ in range(steps):
+                            cap(tok)
+                    return go
+
+                r = rounds_of({"default": stepper(False), "wide": stepper(True)}, rounds, 1)
+                de = [t / steps for t in r["default"]]
+                wi = [t / steps for t in r["wide"]]
+                rat = [a / b for a, b in zip(wi, de)]
+                say(f"B={B} context {S0}..{S0 + steps}: step captured {fmt(de)} /token   wide {fmt(wi)} /token  -> "
+                    f"wide / default = {statistics.median(rat):.3f} ({min(rat):.3f}..{max(rat):.3f}); the default "
+                    f"step's rounds spread {min(de) / statistics.median(de):.3f}..{max(de) / statistics.median(de):.3f} "
+                    "of their median")
+                del cache
+        del model
+    torch.cuda.empty_cache()
+
+
 def section_sampler(dev, rounds):
     say("== 4. token choice in generate(graph=True, temperature=0.8, top_k=40), GPT-2-medium: torch route vs "
         "sampler=\"fused\"")
@@ -434,6 +518,8 @@ def main():
         section_append(dev, a.rounds)
     if "6" in sec:
         section_fused_parts(dev, a.rounds)
+    if "7" in sec:
+        section_wide(dev, a.rounds)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "a" if a.append else "w") as f:
         f.write("\n".join(LINES) + "\n")
