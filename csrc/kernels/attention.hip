@@ -18,6 +18,7 @@
 // one key and gathers the bits across its lane quad. Masking work is skipped on tiles that are entirely
 // below the causal diagonal.
 #include <initializer_list>
+#include <type_traits>
 
 #include "common.h"
 #include "routes.h"
@@ -124,6 +125,41 @@ __device__ __forceinline__ void tile_store(const TileRegs& t, char* lds) {
   for (int u = 0; u < 2; ++u) {
     const int idx = threadIdx.x + 256 * u, row = idx >> 3, c = idx & 7;
     *reinterpret_cast<uint4*>(lds + swz(row, c)) = t.r[u];
+  }
+}
+// The same tile from an fp8 KV cache (attn_decode_fp8.hip: 64 e4m3 codes and one power-of-two f32 scale a row): per
+// thread and piece 8 code bytes and the row's scale, dequantized to bf16 (exactly: 4 significant bits) on the way into
+// the swizzled tile. Rows at or past nrows are zero-filled by select (codes 0, scale 1): the cache is uninitialised
+// there.
+struct TileRegs8 {
+  uint2 r[2];
+  float s[2];
+};
+__device__ __forceinline__ void tile_load(TileRegs8& t, const uint8_t* base, const float* scales, int row0, int nrows) {
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int idx = threadIdx.x + 256 * u, row = idx >> 3, c = idx & 7;
+    if (row0 + row < nrows) {
+      t.r[u] = *reinterpret_cast<const uint2*>(base + (long)(row0 + row) * 64 + c * 8);
+      t.s[u] = scales[row0 + row];
+    } else {
+      t.r[u] = make_uint2(0, 0);
+      t.s[u] = 1.f;
+    }
+  }
+}
+__device__ __forceinline__ void tile_store(const TileRegs8& t, char* lds) {
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int idx = threadIdx.x + 256 * u, row = idx >> 3, c = idx & 7;
+    const f32x2_t a = __builtin_amdgcn_cvt_pk_f32_fp8((int)t.r[u].x, false);
+    const f32x2_t b = __builtin_amdgcn_cvt_pk_f32_fp8((int)t.r[u].x, true);
+    const f32x2_t d = __builtin_amdgcn_cvt_pk_f32_fp8((int)t.r[u].y, false);
+    const f32x2_t e = __builtin_amdgcn_cvt_pk_f32_fp8((int)t.r[u].y, true);
+    const float sc = t.s[u];
+    *reinterpret_cast<uint4*>(lds + swz(row, c)) =
+        make_uint4(pack2bf(a[0] * sc, a[1] * sc), pack2bf(b[0] * sc, b[1] * sc), pack2bf(d[0] * sc, d[1] * sc),
+                   pack2bf(e[0] * sc, e[1] * sc));
   }
 }
 // additive key-mask value (log2 units) of key `key`: -inf past the end
@@ -408,7 +444,11 @@ struct AppendArgs {
 
 // block: 4 waves x 16 queries; grid (cdiv(S, 64), B*H). No heavy/light pairing: every block walks the cached prefix.
 // Every wave takes part in all tile loads and barriers of its block (also one whose 16 queries lie at or past S).
-__global__ void __launch_bounds__(256, 2) attn_append_kernel(AppendArgs a) {
+// FP8: kc / vc point at the e4m3 codes of an fp8 cache and ksc / vsc at its row scales [B, H, Smax]; only the tile
+// loader differs (TileRegs8), so the result is bit for bit that of the bf16 kernel on the dequantized cache.
+template <bool FP8>
+__global__ void __launch_bounds__(256, 2) attn_append_kernel(AppendArgs a, const float* __restrict__ ksc,
+                                                             const float* __restrict__ vsc) {
   __shared__ __attribute__((aligned(16))) char sk[64 * 128];
   __shared__ __attribute__((aligned(16))) char sv[64 * 128];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, G = lane >> 4, i = lane & 15;
@@ -433,19 +473,24 @@ __global__ void __launch_bounds__(256, 2) attn_append_kernel(AppendArgs a) {
   float m = -INFINITY, l = 0.f;
   const int kend = min(Sk, off + min(a.S, blk * 64 + 64));  // >= 1: the block's last valid query's last key, + 1
   const int ntiles = (kend + 63) / 64;
-  TileRegs tk, tv;
-  tile_load(tk, K, HD, 0, Sk);
-  tile_load(tv, V, HD, 0, Sk);
+  std::conditional_t<FP8, TileRegs8, TileRegs> tk, tv;
+  auto load_kv = [&](int row0) {
+    if constexpr (FP8) {
+      tile_load(tk, reinterpret_cast<const uint8_t*>(a.kc) + (long)bh * a.Smax * HD, ksc + (long)bh * a.Smax, row0, Sk);
+      tile_load(tv, reinterpret_cast<const uint8_t*>(a.vc) + (long)bh * a.Smax * HD, vsc + (long)bh * a.Smax, row0, Sk);
+    } else {
+      tile_load(tk, K, HD, row0, Sk);
+      tile_load(tv, V, HD, row0, Sk);
+    }
+  };
+  load_kv(0);
   for (int t = 0; t < ntiles; ++t) {
     __syncthreads();
     tile_store(tk, sk);
     tile_store(tv, sv);
     __syncthreads();
     const int k0 = t * 64;
-    if (t + 1 < ntiles) {
-      tile_load(tk, K, HD, k0 + 64, Sk);
-      tile_load(tv, V, HD, k0 + 64, Sk);
-    }
+    if (t + 1 < ntiles) load_kv(k0 + 64);
     v4f s[4];
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
@@ -1049,9 +1094,29 @@ DTF_API int dtf_attn_append(const void* qkv, const void* k_cache, const void* v_
   if ((long)B * H > 65535) return -1;
   AppendArgs a{(const bf16_t*)qkv, (const bf16_t*)k_cache, (const bf16_t*)v_cache, lens, (bf16_t*)out, B, S, H, Smax,
                scale};
-  hipLaunchKernelGGL(attn_append_kernel, dim3((unsigned)((S + 63) / 64), (unsigned)(B * H)), dim3(256), 0,
-                     (hipStream_t)stream, a);
+  hipLaunchKernelGGL(attn_append_kernel<false>, dim3((unsigned)((S + 63) / 64), (unsigned)(B * H)), dim3(256), 0,
+                     (hipStream_t)stream, a, (const float*)nullptr, (const float*)nullptr);
   count_launch(LC_ATTN_APPEND);
+  return (int)hipGetLastError();
+}
+
+// dtf_attn_append over an fp8 cache (attn_decode_fp8.hip's format): k_cache / v_cache [B, H, Smax, 64] e4m3 codes,
+// k_scale / v_scale [B, H, Smax] f32. The same grid and, after the tile loader, the same code: bit for bit the result
+// of dtf_attn_append on the dequantized cache. -1 as there (code pointers off 16 bytes, scale pointers off 4).
+DTF_API int dtf_attn_append_fp8(const void* qkv, const void* k_cache, const void* v_cache, const float* k_scale,
+                                const float* v_scale, const long* lens, void* out, int B, int S, int H, int Smax,
+                                float scale, void* stream) {
+  if (!qkv || !k_cache || !v_cache || !k_scale || !v_scale || !lens || !out || B < 1 || S < 1 || H < 1 || Smax < 1)
+    return -1;
+  if (!aligned16(qkv) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(out) || ((uintptr_t)lens & 7) ||
+      ((uintptr_t)k_scale & 3) || ((uintptr_t)v_scale & 3))
+    return -1;
+  if ((long)B * H > 65535) return -1;
+  AppendArgs a{(const bf16_t*)qkv, (const bf16_t*)k_cache, (const bf16_t*)v_cache, lens, (bf16_t*)out, B, S, H, Smax,
+               scale};
+  hipLaunchKernelGGL(attn_append_kernel<true>, dim3((unsigned)((S + 63) / 64), (unsigned)(B * H)), dim3(256), 0,
+                     (hipStream_t)stream, a, k_scale, v_scale);
+  count_launch(LC_ATTN_APPEND_FP8);
   return (int)hipGetLastError();
 }
 

@@ -42,7 +42,9 @@ enum LaunchCounter : int {
   LC_DENSE_SKINNY_FUSED = 14,  // attn_decode_fused.hip, dense_skinny with LayerNorm prologue / residual / cache-store epilogue
   LC_ATTN_DECODE_FUSED = 15,   // attn_decode_fused.hip, split-KV attention with the merge in the same launch
   LC_DENSE_WIDE = 16,          // dense_wide.hip, M <= 64 weight-streaming dense
-  LC_COUNT = 17
+  LC_ATTN_DECODE_FP8 = 17,     // attn_decode_fp8.hip, split-KV single-token attention over an fp8 cache
+  LC_ATTN_APPEND_FP8 = 18,     // attention.hip, multi-token append attention over an fp8 cache
+  LC_COUNT = 19
 };
 DTF_API long* dtf_launch_counters();  // gemm.hip
 inline void count_launch(int c) { dtf_launch_counters()[c]++; }

@@ -149,6 +149,11 @@ _KERNEL_SIGS = {
     "dtf_dense_wide_variant": [P, P, P, P, I, I, I, I, I, P],
     # multi-token append attention over the cache (attention.hip): qkv, k, v, lens, out, B, S, H, Smax, scale, stream
     "dtf_attn_append": [P, P, P, P, P, I, I, I, I, F, P],
+    # the fp8 KV cache (attn_decode_fp8.hip, attention.hip): the bf16 entry points' arguments with k_scale, v_scale
+    # after k, v
+    "dtf_kv_store_fp8": [P, P, P, P, P, P, I, I, I, I, P],
+    "dtf_attn_decode_fp8": [P, P, P, P, P, P, P, P, I, I, I, F, P],
+    "dtf_attn_append_fp8": [P, P, P, P, P, P, P, I, I, I, I, F, P],
     # fused token sampler (sample.hip): logits, f32, ld, B, n, 1/T, greedy, top_k, P, r, 1/r, seed, uniform, table, out,
     # width, pos, done, eos, pad, tok_out, stream
     "dtf_sample_logits": [P, I, L, I, I, F, I, I, I, F, F, U, P, P, P, L, P, P, L, L, P, P],

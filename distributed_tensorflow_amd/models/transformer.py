@@ -283,6 +283,8 @@ class GPT2(Model):
             x = ops.embedding(ids, self.wte, self.wpe, position_ids=pos.clamp_(0, top))
         if fused and S == 1:
             self._check_fused(ids.shape[0], ids.device)
+            if cache.fp8:
+                raise ValueError("the fused decode step has no kernels for an fp8 KV cache")
             for i, b in enumerate(self.blocks):
                 x = b(x, training=False, cache=cache, layer=i, fused=True)
             return x
@@ -402,12 +404,13 @@ class GPT2(Model):
             return decode_ops.step_dense(h, self.wte, self.pad_bias, wide=wide)
         return ops.dense(h, self.wte, self.pad_bias)
 
-    def new_cache(self, batch, capacity, device, chunked=False):
+    def new_cache(self, batch, capacity, device, chunked=False, kv_dtype=None):
         """A KV cache for this model. chunked=True: on the GPU multi-token pieces behind a filled cache run the append
-        kernel (extend(chunk=N), generate(cache=, prefill_chunk=N)); a default cache refuses them."""
+        kernel (extend(chunk=N), generate(cache=, prefill_chunk=N)); a default cache refuses them. kv_dtype="fp8":
+        e4m3 codes with a power-of-two scale per cached row (ops.decode) instead of bf16 (None / "bf16")."""
         c = self.cfg
         return decode_ops.KVCache(c["layers"], batch, c["heads"], capacity, device, head_dim=c["hidden"] // c["heads"],
-                                  chunked=chunked)
+                                  chunked=chunked, kv_dtype=kv_dtype)
 
     def _pick(self, logits, temperature, top_k, gen):
         """Next token per row from logits [B, vocab_p]: argmax, or temperature / top-k sampling, over the real
@@ -423,7 +426,7 @@ class GPT2(Model):
 
     def generate(self, ids, max_new_tokens, *, prompt_lens=None, temperature=0.0, top_k=None, seed=None,
                  eos_token_id=None, pad_token_id=None, graph=True, cache=None, prefill_chunk=None, top_p=None,
-                 repetition_penalty=None, sampler=None, step=None):
+                 repetition_penalty=None, sampler=None, step=None, kv_dtype=None):
         """Continue `ids` [B, S0] by max_new_tokens tokens with a KV cache -> int64 [B, S0 + max_new_tokens].
 
         cache: a KVCache to continue (``last_generation["cache"]`` of an earlier call, or one filled through
@@ -458,10 +461,22 @@ class GPT2(Model):
         step="wide" runs the projections of the one-token step (four a layer and the LM head) on ``ops.dense_wide``, the
         weight stream for 17 to 64 rows, when 16 < batch <= 64; up to 16 rows it is the default step, bit for bit.
         Batch > 64 or a hidden size that is no multiple of 8 raises ValueError before anything is computed.
-        Default None: the step described above, unchanged (past 16 rows its projections run ``ops.dense``)."""
+        Default None: the step described above, unchanged (past 16 rows its projections run ``ops.dense``).
+
+        kv_dtype="fp8": the cache this call creates (on the plain and the prefill_chunk route) stores K and V as e4m3
+        codes with one power-of-two scale per cached row, 68 bytes a row instead of 128 (``ops.decode``); the decode
+        step and chunked prefill read it with the fp8 attention kernels, prefill attention itself stays on the bf16
+        projection. With cache= it must name that cache's dtype. step="fused" has no fp8-cache kernels. Both raise
+        ValueError before anything is computed. Default None: bf16 (or the dtype of the cache passed in)."""
         if step not in (None, "fused", "wide"):
             raise ValueError(f"generate: step {step!r} (None, 'fused' or 'wide')")
+        if kv_dtype not in (None, "bf16", "fp8"):
+            raise ValueError(f"generate: kv_dtype {kv_dtype!r} (None, 'bf16' or 'fp8')")
+        if cache is not None and kv_dtype is not None and kv_dtype != cache.kv_dtype:
+            raise ValueError(f"generate: kv_dtype {kv_dtype!r} against a {cache.kv_dtype} cache")
         step_fused, step_wide = step == "fused", step == "wide"
+        if step_fused and (kv_dtype == "fp8" or (cache is not None and cache.fp8)):
+            raise ValueError("generate: step='fused' has no kernels for an fp8 KV cache")
         if step_fused:
             self._check_fused(ids.shape[0], ids.device)
         if step_wide:
@@ -502,7 +517,7 @@ class GPT2(Model):
             else:
                 plens = torch.as_tensor(prompt_lens).to(dev).long()
             if cache is None and prefill_chunk is None:
-                cache = self.new_cache(B, S0 + n_new, dev)
+                cache = self.new_cache(B, S0 + n_new, dev, kv_dtype=kv_dtype)
                 h = self._hidden_cached(ids, cache)  # prefill: K/V of all S0 positions; a pad position is rewritten
                 cache.set_lens(plens)                # by the decode step that reaches it before anything attends to it
                 rows = plens - 1 + torch.arange(B, device=dev) * S0
@@ -510,7 +525,7 @@ class GPT2(Model):
                 logits = self._lm_head(last.reshape(B, 1, -1), decode=True)[:, 0]
             else:
                 if cache is None:  # (prefill_chunk given: the pieces after the first land behind a filled cache)
-                    cache = self.new_cache(B, S0 + n_new, dev, chunked=True)
+                    cache = self.new_cache(B, S0 + n_new, dev, chunked=True, kv_dtype=kv_dtype)
                 logits = self.extend(ids, cache, plens, prefill_chunk)  # behind what the cache holds, in pieces
 
             def one_token(tok):

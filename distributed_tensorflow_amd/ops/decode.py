@@ -3,7 +3,7 @@ attn_decode_fused.hip).
 
 A decode step computes one token per sequence: its attention reads the keys and values of every earlier position
 (a memory-bound stream over the cache) and its projections read every weight once for at most 16 rows of activations
-(a weight stream). ``KVCache`` owns K and V of all layers as ``[layers, B, H, Smax, 64]`` bf16, one ``lens[B]`` int64
+(a weight stream). ``KVCache`` owns K and V of all layers as ``[layers, B, H, Smax, 64]`` bf16 (or fp8 codes, below), one ``lens[B]`` int64
 tensor shared by the layers (valid positions per batch row; also the position ids of the step's embedding) and the
 split-KV scratch. Per layer a step calls ``store`` (append at ``lens``), then ``attend``; the caller ``advance``s
 ``lens`` once per token. Nothing reads a device value on the host, so a step is hipGraph-capturable.
@@ -11,6 +11,12 @@ split-KV scratch. Per layer a step calls ``store`` (append at ``lens``), then ``
 CPU reference of appending a multi-token chunk to a filled cache. On the GPU S == 1 is ``attend``; S > 1 runs the
 multi-token append kernel (``dtf_attn_append``, csrc/kernels/attention.hip) on a cache built with ``chunked=True`` and
 raises on a default cache (the route is opt-in per cache for now).
+
+``KVCache(kv_dtype="fp8")`` stores every cached row (64 values of one layer, batch row, head and position) as 64 OCP
+e4m3 codes and one power-of-two f32 scale, 68 bytes instead of 128 (csrc/kernels/attn_decode_fp8.hip; the format is
+``kv_quantize_reference``). ``store``, ``attend`` and ``attend_chunk`` route by the cache's dtype; the fused step's
+launches (``attend(fused=True)``, ``dense_skinny_fused(store=)``) have no fp8 variant and raise ValueError. On the CPU
+an fp8 cache holds the dequantized values in f32: ``store`` rounds through the format, everything else is unchanged.
 
 ``dense_skinny`` is an explicit route: ``ops.dense`` / ``ops.gemm`` dispatch as before and never reach it.
 ``dense_skinny_fused`` and ``KVCache.attend(fused=True)`` are the launches of the fused one-token step
@@ -37,8 +43,30 @@ def decode_chunk():
     return int(K().dtf_attn_decode_chunk())
 
 
+def kv_quantize_reference(x):
+    """The fp8 KV-cache format in plain torch on the CPU: x [..., 64] -> (codes uint8 [..., 64], scale f32 [...]).
+    scale = 2^e with a = the row's largest finite |v| = m * 2^x (1 <= m < 2): e = x - 8 if m <= 1.75 else x - 7 (the
+    smallest e with a * 2^-e <= 448), at least -64, and 0 for a == 0. code = e4m3fn(clamp(v * 2^-e, +-448)), rounded
+    to nearest even; NaN stays a NaN code, +-inf saturates."""
+    x = x.detach().float().cpu()
+    a = torch.where(torch.isfinite(x), x.abs(), torch.zeros_like(x)).amax(-1)
+    mant, exp = torch.frexp(a)                      # a = mant * 2^exp, 0.5 <= mant < 1: m = 2 mant, x = exp - 1
+    e = exp - 9 + (mant > 0.875).to(exp.dtype)
+    e = torch.where(a == 0, torch.zeros_like(e), e.clamp(min=-64))
+    y = torch.ldexp(x, -e[..., None]).clamp(-448.0, 448.0)   # exact; torch.clamp keeps NaN
+    return y.to(torch.float8_e4m3fn).view(torch.uint8), torch.ldexp(torch.ones_like(a), e)
+
+
+def _kv_dequantize(codes, scale):
+    return codes.view(torch.float8_e4m3fn).float() * scale[..., None]
+
+
 class KVCache:
-    def __init__(self, layers, batch, heads, capacity, device, head_dim=HEAD_DIM, chunked=False):
+    def __init__(self, layers, batch, heads, capacity, device, head_dim=HEAD_DIM, chunked=False, kv_dtype=None):
+        if kv_dtype not in (None, "bf16", "fp8"):
+            raise ValueError(f"KVCache: kv_dtype {kv_dtype!r} (None, 'bf16' or 'fp8')")
+        self.kv_dtype = kv_dtype or "bf16"
+        self.fp8 = self.kv_dtype == "fp8"
         self.device = torch.device(device)
         gpu = self.device.type == "cuda"
         if gpu and head_dim != HEAD_DIM:
@@ -47,8 +75,13 @@ class KVCache:
         self.capacity = (int(capacity) + 63) // 64 * 64
         shape = (self.layers, self.batch, self.heads, self.capacity, self.head_dim)
         # GPU: uninitialised (the kernels never let a position past lens reach the arithmetic); CPU reference: zeros
-        self.k = torch.empty(shape, dtype=BF16, device=self.device) if gpu else torch.zeros(shape, dtype=F32)
-        self.v = torch.empty(shape, dtype=BF16, device=self.device) if gpu else torch.zeros(shape, dtype=F32)
+        self.k_scale = self.v_scale = None
+        if gpu and self.fp8:  # e4m3 codes and one f32 power-of-two scale per cached row
+            self.k, self.v = (torch.empty(shape, dtype=torch.uint8, device=self.device) for _ in range(2))
+            self.k_scale, self.v_scale = (torch.empty(shape[:-1], dtype=F32, device=self.device) for _ in range(2))
+        else:
+            self.k = torch.empty(shape, dtype=BF16, device=self.device) if gpu else torch.zeros(shape, dtype=F32)
+            self.v = torch.empty(shape, dtype=BF16, device=self.device) if gpu else torch.zeros(shape, dtype=F32)
         self.lens = torch.zeros(self.batch, dtype=torch.int64, device=self.device)
         self.empty = True  # host-side: nothing stored since the last reset
         # GPU: attend_chunk with S > 1 runs the append kernel (False: it raises); the CPU path takes any S either way
@@ -77,6 +110,10 @@ class KVCache:
         if on_gpu(qkv):
             q = qkv if qkv.dtype == BF16 else qkv.to(BF16)
             q = q.contiguous()
+            if self.fp8:
+                call("dtf_kv_store_fp8", ptr(q), ptr(self.k[layer]), ptr(self.v[layer]), ptr(self.k_scale[layer]),
+                     ptr(self.v_scale[layer]), ptr(self.lens), B, S, self.heads, self.capacity, stream(qkv.device))
+                return
             call("dtf_kv_store", ptr(q), ptr(self.k[layer]), ptr(self.v[layer]), ptr(self.lens), B, S, self.heads,
                  self.capacity, stream(qkv.device))
             return
@@ -84,6 +121,8 @@ class KVCache:
         bi, si = torch.nonzero(pos < self.capacity, as_tuple=True)
         pi = pos[bi, si]
         x = qkv.float().reshape(B, S, 3, self.heads, self.head_dim)
+        if self.fp8:  # the reference of the fp8 store: the values the format keeps
+            x = _kv_dequantize(*kv_quantize_reference(x))
         self.k[layer][bi, :, pi] = x[bi, si, 1]
         self.v[layer][bi, :, pi] = x[bi, si, 2]
 
@@ -92,6 +131,8 @@ class KVCache:
         (store first: the token's own key is position lens[b]) -> [B, 1, H*D]. fused=True (GPU): one launch, the
         split-KV merge done by the last block of each head; the same bits as the two-launch default."""
         self._check(layer, qkv, 1)
+        if fused and self.fp8:
+            raise ValueError("attend(fused=True): the one-launch decode attention has no fp8-cache variant")
         B = self.batch
         HD = self.heads * self.head_dim
         scale = float(scale) if scale is not None else 1.0 / math.sqrt(self.head_dim)
@@ -102,6 +143,11 @@ class KVCache:
             if fused:
                 call("dtf_attn_decode_fused", ptr(q), ptr(self.k[layer]), ptr(self.v[layer]), ptr(self.lens), ptr(out),
                      ptr(self.scratch), ptr(self.counters), B, self.heads, self.capacity, scale, stream(qkv.device))
+                return out
+            if self.fp8:
+                call("dtf_attn_decode_fp8", ptr(q), ptr(self.k[layer]), ptr(self.v[layer]), ptr(self.k_scale[layer]),
+                     ptr(self.v_scale[layer]), ptr(self.lens), ptr(out), ptr(self.scratch), B, self.heads,
+                     self.capacity, scale, stream(qkv.device))
                 return out
             call("dtf_attn_decode", ptr(q), ptr(self.k[layer]), ptr(self.v[layer]), ptr(self.lens), ptr(out),
                  ptr(self.scratch), B, self.heads, self.capacity, scale, stream(qkv.device))
@@ -135,6 +181,11 @@ class KVCache:
             q = qkv if qkv.dtype == BF16 else qkv.to(BF16)
             q = q.contiguous()
             out = torch.empty(B, S, HD, dtype=BF16, device=qkv.device)
+            if self.fp8:
+                call("dtf_attn_append_fp8", ptr(q), ptr(self.k[layer]), ptr(self.v[layer]), ptr(self.k_scale[layer]),
+                     ptr(self.v_scale[layer]), ptr(self.lens), ptr(out), B, S, self.heads, self.capacity, scale,
+                     stream(qkv.device))
+                return out
             call("dtf_attn_append", ptr(q), ptr(self.k[layer]), ptr(self.v[layer]), ptr(self.lens), ptr(out), B, S,
                  self.heads, self.capacity, scale, stream(qkv.device))
             return out
@@ -145,6 +196,14 @@ class KVCache:
         p = torch.softmax(s.masked_fill(dead[:, None], float("-inf")), -1)
         o = torch.matmul(p, self.v[layer])                                                     # [B, H, S, D]
         return o.transpose(1, 2).reshape(B, S, HD).to(qkv.dtype)
+
+    def dequantized(self, layer):
+        """(K, V) of `layer` in f32, [B, H, capacity, D]: code * scale for an fp8 cache on the GPU, else the plain
+        values (uninitialised rows of a GPU cache included, whatever they hold)."""
+        if self.fp8 and self.k_scale is not None:
+            return (_kv_dequantize(self.k[layer], self.k_scale[layer]),
+                    _kv_dequantize(self.v[layer], self.v_scale[layer]))
+        return self.k[layer].float(), self.v[layer].float()
 
     def advance(self, n=1):
         self.lens.add_(n)
@@ -225,6 +284,8 @@ def dense_skinny_fused(x, w, bias=None, act=None, *, ln=None, residual=None, sto
     CPU tensors take the explicit f32 composition of the same steps."""
     a = act_code(act)
     cache, layer = store if store is not None else (None, None)
+    if cache is not None and getattr(cache, "fp8", False):
+        raise ValueError("dense_skinny_fused(store=): the cache-store epilogue has no fp8-cache variant")
     if not on_gpu(x):
         h = x
         if ln is not None:

@@ -24,6 +24,10 @@ min..max spread over the rounds is reported; times are host clocks around work t
  7. (--sections 7) past 16 rows: ops.dense_wide, and each (R, T) variant of its kernel, against ops.dense at M = 17,
     32, 48, 64 on the same shapes (as section 3), and the captured one-token step at B = 32 and 64, context ~350 and
     ~1000, default against wide=True (generate(step="wide")).
+ 8. (--sections 8) the fp8 KV cache (kv_dtype="fp8") against the bf16 one: KVCache.attend alone at B in {1, 8, 32, 64},
+    cached length 256 and 768, H = 16, capacity 1024 (as section 2: a replayed graph over layers that rotate through
+    HBM) with the K + V + scale bytes of the valid rows over its time; the captured one-token step of GPT-2-medium,
+    default at B = 8 and wide at B = 32 and 64, context ~350 and ~1000; and the cache bytes at B = 64.
 """
 import argparse
 import os
@@ -348,6 +352,87 @@ def section_wide(dev, rounds):
     torch.cuda.empty_cache()
 
 
+def _fill(cache, n):
+    """Arbitrary finite contents (fp8: codes below the NaN code, scale 2^-6) and lens = n."""
+    if cache.fp8:
+        for codes, sc in ((cache.k, cache.k_scale), (cache.v, cache.v_scale)):
+            codes.random_(0, 0x78)
+            sc.fill_(2.0 ** -6)
+    else:
+        cache.k.normal_()
+        cache.v.normal_()
+    cache.empty = False
+    cache.lens.fill_(n)
+
+
+def section_kv_fp8(dev, rounds):
+    say("== 8. fp8 KV cache (e4m3 codes + one f32 power-of-two scale a row, 68 B) against bf16 (128 B)")
+    H, cap = 16, 1024
+    say(f"KVCache.attend alone, H = {H}, capacity {cap}, inside a replayed graph over layers rotating through HBM; "
+        "bytes: K + V (+ scales) of the valid rows")
+    with torch.no_grad():
+        for B in (1, 8, 32, 64):
+            layers = max(2, min(16, -(-(537 << 20) // (2 * B * H * cap * 128))))
+            caches = {d: ops.KVCache(layers, B, H, cap, dev, kv_dtype=d) for d in ("bf16", "fp8")}
+            qkv = torch.randn(B, 1, 3 * H * 64, device=dev).to(torch.bfloat16)
+            for L in (256, 768):
+                arms = {}
+                for d, cache in caches.items():
+                    _fill(cache, L - 1)
+                    arms[d] = graph_of(lambda cache=cache: [cache.attend(l, qkv) for l in range(layers)])
+                res = rounds_of(arms, rounds, 20)
+                line = f"B={B:2d} L={L}: "
+                for d, row in (("bf16", 128), ("fp8", 68)):
+                    ts = [t / layers for t in res[d]]
+                    nbytes = 2 * B * H * L * row
+                    bw = nbytes / statistics.median(ts)
+                    line += (f"{d} {fmt(ts, 1e6, 'us')} {nbytes / 1e6:6.2f} MB {bw / 1e12:.2f} TB/s "
+                             f"{100 * bw / COPY_BW:3.0f}%   ")
+                say(line + f"fp8 / bf16 = {statistics.median(res['fp8']) / statistics.median(res['bf16']):.2f}")
+            del caches, arms
+            torch.cuda.empty_cache()
+    say("per token: the captured one-token step of GPT-2-medium, bf16 against fp8 cache, alternating inside each round")
+    with context.device(dev), torch.no_grad():
+        model = gpt2_medium(dropout=0.0)
+        for B, wide in ((8, False), (32, True), (64, True)):
+            for L in (384, 1024):
+                S0, steps = L - 32, 24
+                torch.manual_seed(B * 10000 + L)
+                tok = torch.randint(0, model.vocab, (B, 1), device=dev)
+
+                def stepper(cache):
+                    def step(t):
+                        lg = model(t, training=False, cache=cache, wide=wide)
+                        cache.advance(1)
+                        return lg
+                    cap_ = CapturedStep(step, split=False)
+                    for _ in range(4):
+                        cap_(tok)
+                    assert cap_.captured
+
+                    def go():
+                        cache.lens.fill_(S0)  # stay at context S0 .. S0 + steps
+                        for _ in range(steps):
+                            cap_(tok)
+                    return go
+
+                caches = {d: model.new_cache(B, L, dev, kv_dtype=d) for d in ("bf16", "fp8")}
+                for cache in caches.values():
+                    _fill(cache, S0)
+                r = rounds_of({d: stepper(c) for d, c in caches.items()}, rounds, 1)
+                bf, f8 = ([t / steps for t in r[d]] for d in ("bf16", "fp8"))
+                rat = [a / b for a, b in zip(f8, bf)]
+                say(f"B={B} {'wide' if wide else 'default'} step, context {S0}..{S0 + steps}: bf16 {fmt(bf)} /token   "
+                    f"fp8 {fmt(f8)} /token  -> fp8 / bf16 = {statistics.median(rat):.3f} ({min(rat):.3f}..{max(rat):.3f})")
+                del caches
+        c = model.cfg
+        rows = 2 * c["layers"] * 64 * c["heads"] * 1024
+        say(f"cache bytes, GPT-2-medium, B = 64, capacity 1024: bf16 {rows * 128 / 1e9:.2f} GB, fp8 {rows * 68 / 1e9:.2f} GB "
+            "(codes + scales)")
+        del model
+    torch.cuda.empty_cache()
+
+
 def section_sampler(dev, rounds):
     say("== 4. token choice in generate(graph=True, temperature=0.8, top_k=40), GPT-2-medium: torch route vs "
         "sampler=\"fused\"")
@@ -520,6 +605,8 @@ def main():
         section_fused_parts(dev, a.rounds)
     if "7" in sec:
         section_wide(dev, a.rounds)
+    if "8" in sec:
+        section_kv_fp8(dev, a.rounds)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "a" if a.append else "w") as f:
         f.write("\n".join(LINES) + "\n")
