@@ -154,6 +154,9 @@ _KERNEL_SIGS = {
     "dtf_kv_store_fp8": [P, P, P, P, P, P, I, I, I, I, P],
     "dtf_attn_decode_fp8": [P, P, P, P, P, P, P, P, I, I, I, F, P],
     "dtf_attn_append_fp8": [P, P, P, P, P, P, P, I, I, I, I, F, P],
+    # shared-prefix decode attention (attn_decode_shared.hip): qkv, k_prefix, v_prefix, k_own, v_own, plens, lens, out,
+    # scratch, B0, G, H, Smax_prefix, Smax_own, scale, stream
+    "dtf_attn_decode_shared": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, P],
     # fused token sampler (sample.hip): logits, f32, ld, B, n, 1/T, greedy, top_k, P, r, 1/r, seed, uniform, table, out,
     # width, pos, done, eos, pad, tok_out, stream
     "dtf_sample_logits": [P, I, L, I, I, F, I, I, I, F, F, U, P, P, P, L, P, P, L, L, P, P],

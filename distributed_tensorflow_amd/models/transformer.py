@@ -407,7 +407,8 @@ class GPT2(Model):
     def new_cache(self, batch, capacity, device, chunked=False, kv_dtype=None):
         """A KV cache for this model. chunked=True: on the GPU multi-token pieces behind a filled cache run the append
         kernel (extend(chunk=N), generate(cache=, prefill_chunk=N)); a default cache refuses them. kv_dtype="fp8":
-        e4m3 codes with a power-of-two scale per cached row (ops.decode) instead of bf16 (None / "bf16")."""
+        e4m3 codes with a power-of-two scale per cached row (ops.decode) instead of bf16 (None / "bf16"). A filled bf16
+        cache can be forked for several continuations per row (``cache.fork(G)``, generate(num_return_sequences=G))."""
         c = self.cfg
         return decode_ops.KVCache(c["layers"], batch, c["heads"], capacity, device, head_dim=c["hidden"] // c["heads"],
                                   chunked=chunked, kv_dtype=kv_dtype)
@@ -426,7 +427,7 @@ class GPT2(Model):
 
     def generate(self, ids, max_new_tokens, *, prompt_lens=None, temperature=0.0, top_k=None, seed=None,
                  eos_token_id=None, pad_token_id=None, graph=True, cache=None, prefill_chunk=None, top_p=None,
-                 repetition_penalty=None, sampler=None, step=None, kv_dtype=None):
+                 repetition_penalty=None, sampler=None, step=None, kv_dtype=None, num_return_sequences=None):
         """Continue `ids` [B, S0] by max_new_tokens tokens with a KV cache -> int64 [B, S0 + max_new_tokens].
 
         cache: a KVCache to continue (``last_generation["cache"]`` of an earlier call, or one filled through
@@ -467,7 +468,21 @@ class GPT2(Model):
         codes with one power-of-two scale per cached row, 68 bytes a row instead of 128 (``ops.decode``); the decode
         step and chunked prefill read it with the fp8 attention kernels, prefill attention itself stays on the bf16
         projection. With cache= it must name that cache's dtype. step="fused" has no fp8-cache kernels. Both raise
-        ValueError before anything is computed. Default None: bf16 (or the dtype of the cache passed in)."""
+        ValueError before anything is computed. Default None: bf16 (or the dtype of the cache passed in).
+
+        num_return_sequences=G (2..16): G continuations of every prompt -> [B * G, S0 + max_new_tokens], row b * G + j
+        the j-th sample of prompt b. The prompt is prefilled once at batch B and its K/V kept once: the cache is
+        forked (``KVCache.fork``) and the token loop runs at B * G rows, each decode attention reading the prompt once
+        per group (``dtf_attn_decode_shared``) and the row's own new positions behind it. Row b * G + j draws what row
+        b * G + j of ``ids.repeat_interleave(G, 0)`` would draw. Every sampler, graph= and step="wide" apply;
+        cache=, prefill_chunk=, step="fused", kv_dtype="fp8" and G > 16 raise ValueError before anything is computed.
+        ``last_generation["cache"]`` is the fork (its ``prefix`` the prompt's cache). None or 1: one row per prompt."""
+        G = 1 if num_return_sequences is None else int(num_return_sequences)
+        if G < 1 or G > 16:
+            raise ValueError(f"generate: num_return_sequences {num_return_sequences} (1..16)")
+        if G > 1 and (cache is not None or prefill_chunk is not None or step == "fused" or kv_dtype == "fp8"):
+            raise ValueError("generate: num_return_sequences > 1 runs on a forked bf16 cache of its own: not with "
+                             "cache=, prefill_chunk=, step='fused' or kv_dtype='fp8'")
         if step not in (None, "fused", "wide"):
             raise ValueError(f"generate: step {step!r} (None, 'fused' or 'wide')")
         if kv_dtype not in (None, "bf16", "fp8"):
@@ -480,7 +495,7 @@ class GPT2(Model):
         if step_fused:
             self._check_fused(ids.shape[0], ids.device)
         if step_wide:
-            self._check_wide(ids.shape[0], ids.device)
+            self._check_wide(ids.shape[0] * G, ids.device)
         if sampler not in (None, "torch", "fused"):
             raise ValueError(f"generate: sampler {sampler!r} (None, 'torch' or 'fused')")
         if sampler == "torch" and (top_p is not None or repetition_penalty is not None):
@@ -505,7 +520,7 @@ class GPT2(Model):
                 raise ValueError(f"cached tokens ({held}) + new tokens ({S0}) + max_new_tokens ({n_new}) exceed "
                                  f"min(cache capacity {cache.capacity}, context length {ctx})")
         if n_new == 0 and cache is None:
-            return ids.clone()
+            return ids.repeat_interleave(G, 0) if G > 1 else ids.clone()
         pad = pad_token_id if pad_token_id is not None else (eos_token_id if eos_token_id is not None else 0)
         gen = None
         if temperature and not fused:
@@ -523,6 +538,10 @@ class GPT2(Model):
                 rows = plens - 1 + torch.arange(B, device=dev) * S0
                 last = ops.gather_rows(h.reshape(B * S0, -1), rows)  # each row's own last prompt position
                 logits = self._lm_head(last.reshape(B, 1, -1), decode=True)[:, 0]
+                if G > 1:  # G rows per prompt from here on; the prompt's K/V stay where they are
+                    cache = cache.fork(G)
+                    ids, plens, logits = (t.repeat_interleave(G, 0) for t in (ids, plens, logits))
+                    B *= G
             else:
                 if cache is None:  # (prefill_chunk given: the pieces after the first land behind a filled cache)
                     cache = self.new_cache(B, S0 + n_new, dev, chunked=True, kv_dtype=kv_dtype)

@@ -18,6 +18,12 @@ e4m3 codes and one power-of-two f32 scale, 68 bytes instead of 128 (csrc/kernels
 launches (``attend(fused=True)``, ``dense_skinny_fused(store=)``) have no fp8 variant and raise ValueError. On the CPU
 an fp8 cache holds the dequantized values in f32: ``store`` rounds through the format, everything else is unchanged.
 
+``KVCache.fork(G)`` serves G continuations of one prompt (``GPT2.generate(num_return_sequences=G)``): the fork has
+batch B0 * G and K/V of its own for the new tokens only, and keeps the filled parent as a read-only prefix. Its
+``attend`` (csrc/kernels/attn_decode_shared.hip) reads the prompt's keys and values once per group, the G queries
+against a key tile on the MFMA, and each row's own positions with the split-KV pass; both write partials that one merge
+sums in a fixed order. bf16 caches and groups of 2 to 16 only; ``attend(fused=True)`` and multi-token chunks raise.
+
 ``dense_skinny`` is an explicit route: ``ops.dense`` / ``ops.gemm`` dispatch as before and never reach it.
 ``dense_skinny_fused`` and ``KVCache.attend(fused=True)`` are the launches of the fused one-token step
 (``GPT2.generate(step="fused")``): the same kernels with LayerNorm, the residual add, the cache append and the split-KV
@@ -92,6 +98,35 @@ class KVCache:
             self.scratch = torch.empty(self.batch * self.heads * self.nchunks * PART, dtype=F32, device=self.device)
             # attend(fused=True): one ticket counter per (b, h); zero here, and every call leaves them zero
             self.counters = torch.zeros(self.batch * self.heads, dtype=torch.int32, device=self.device)
+        # set by fork(): group > 1 marks a forked cache; on the GPU prefix is the parent and plens its lengths
+        self.group, self.prefix, self.plens = 1, None, None
+
+    def fork(self, group):
+        """A cache of batch B0 * group for `group` continuations of every row of this (filled, bf16) cache: row
+        b0 * group + j continues row b0. Same capacity, layers and heads. On the GPU nothing is copied: the new cache
+        has uninitialised K/V of its own for positions from plens = lens.clone() on and keeps this cache by reference
+        as its read-only `prefix`; `attend` reads positions below plens[b0] once per group from the prefix
+        (dtf_attn_decode_shared). Do not write to the parent while a fork is in use. On the CPU the parent's rows are
+        repeated into a plain f32 cache: the reference semantics. ValueError for an empty, fp8 or already forked cache
+        and for a group outside 2..16."""
+        G = int(group)
+        if not 2 <= G <= 16:
+            raise ValueError(f"KVCache.fork: group {group} (2..16)")
+        if self.fp8:
+            raise ValueError("KVCache.fork: the shared-prefix attention has no fp8-cache variant")
+        if self.empty:
+            raise ValueError("KVCache.fork: the cache is empty (prefill it first)")
+        if self.group > 1:
+            raise ValueError("KVCache.fork: this cache is a fork already")
+        c = KVCache(self.layers, self.batch * G, self.heads, self.capacity, self.device, head_dim=self.head_dim)
+        c.group, c.plens, c.empty = G, self.lens.clone(), False
+        c.lens = c.plens.repeat_interleave(G)
+        if self.device.type == "cuda":
+            c.prefix = self
+            c.scratch = torch.empty(2 * c.scratch.numel(), dtype=F32, device=self.device)  # a prefix and a suffix half
+        else:
+            c.k, c.v = self.k.repeat_interleave(G, 1), self.v.repeat_interleave(G, 1)
+        return c
 
     def _check(self, layer, qkv, S=None):
         B, s, T = qkv.shape
@@ -133,6 +168,8 @@ class KVCache:
         self._check(layer, qkv, 1)
         if fused and self.fp8:
             raise ValueError("attend(fused=True): the one-launch decode attention has no fp8-cache variant")
+        if fused and self.group > 1:
+            raise ValueError("attend(fused=True): the one-launch decode attention has no forked-cache variant")
         B = self.batch
         HD = self.heads * self.head_dim
         scale = float(scale) if scale is not None else 1.0 / math.sqrt(self.head_dim)
@@ -140,6 +177,12 @@ class KVCache:
             q = qkv if qkv.dtype == BF16 else qkv.to(BF16)
             q = q.contiguous()
             out = torch.empty(B, 1, HD, dtype=BF16, device=qkv.device)
+            if self.prefix is not None:  # a fork: positions below plens come from the parent, once per group
+                pre = self.prefix
+                call("dtf_attn_decode_shared", ptr(q), ptr(pre.k[layer]), ptr(pre.v[layer]), ptr(self.k[layer]),
+                     ptr(self.v[layer]), ptr(self.plens), ptr(self.lens), ptr(out), ptr(self.scratch), pre.batch,
+                     self.group, self.heads, pre.capacity, self.capacity, scale, stream(qkv.device))
+                return out
             if fused:
                 call("dtf_attn_decode_fused", ptr(q), ptr(self.k[layer]), ptr(self.v[layer]), ptr(self.lens), ptr(out),
                      ptr(self.scratch), ptr(self.counters), B, self.heads, self.capacity, scale, stream(qkv.device))
@@ -171,6 +214,8 @@ class KVCache:
         B, S, _ = qkv.shape
         if S == 1:
             return self.attend(layer, qkv, scale)
+        if self.group > 1:
+            raise ValueError(f"attend_chunk: a forked cache takes one token per row, got {S}")
         HD = self.heads * self.head_dim
         scale = float(scale) if scale is not None else 1.0 / math.sqrt(self.head_dim)
         if on_gpu(qkv):

@@ -28,6 +28,10 @@ min..max spread over the rounds is reported; times are host clocks around work t
     cached length 256 and 768, H = 16, capacity 1024 (as section 2: a replayed graph over layers that rotate through
     HBM) with the K + V + scale bytes of the valid rows over its time; the captured one-token step of GPT-2-medium,
     default at B = 8 and wide at B = 32 and 64, context ~350 and ~1000; and the cache bytes at B = 64.
+ 9. (--sections 9) G = 16 samples per prompt: KVCache.attend on a forked cache (the prompt's K/V read once per group)
+    against a plain cache of the same B0*G rows, B0 in {1, 4}, prefix 256 and 768, suffix 16 and 64 (as section 2: a
+    replayed graph over layers that rotate through HBM), and generate(num_return_sequences=16) against generate on
+    ids.repeat_interleave(16, 0) at 4 prompts of 768 tokens.
 """
 import argparse
 import os
@@ -433,6 +437,55 @@ def section_kv_fp8(dev, rounds):
     torch.cuda.empty_cache()
 
 
+def section_shared_prefix(dev, rounds):
+    say("== 9. shared-prefix decode attention (KVCache.fork, generate(num_return_sequences=G)) against repeated prompts")
+    H, cap, G = 16, 1024, 16
+    say(f"KVCache.attend alone, G = {G}, H = {H}, capacity {cap}, inside a replayed graph over layers rotating through "
+        "HBM: a fork (prefix read once per group) against a plain cache of the same B0*G rows")
+    with torch.no_grad():
+        for B0 in (1, 4):
+            B = B0 * G
+            layers = max(2, min(16, -(-(537 << 20) // (2 * B * H * cap * 128))))
+            parent, plain = ops.KVCache(layers, B0, H, cap, dev), ops.KVCache(layers, B, H, cap, dev)
+            qkv = torch.randn(B, 1, 3 * H * 64, device=dev).to(torch.bfloat16)
+            for Lp in (256, 768):
+                _fill(parent, Lp)
+                fork = parent.fork(G)
+                fork.k.normal_()
+                fork.v.normal_()
+                for Ls in (16, 64):
+                    _fill(plain, Lp + Ls - 1)
+                    fork.lens.fill_(Lp + Ls - 1)
+                    arms = {"plain": graph_of(lambda: [plain.attend(l, qkv) for l in range(layers)]),
+                            "fork": graph_of(lambda: [fork.attend(l, qkv) for l in range(layers)])}
+                    res = rounds_of(arms, rounds, 20)
+                    pl, fk = ([t / layers for t in res[k]] for k in ("plain", "fork"))
+                    rat = [a / b for a, b in zip(fk, pl)]
+                    mb = [2 * H * n * 128 / 1e6 for n in (B * (Lp + Ls), B0 * Lp + B * Ls)]
+                    say(f"B0={B0} x G={G} prefix {Lp} suffix {Ls}: plain {fmt(pl, 1e6, 'us')} {mb[0]:6.2f} MB   "
+                        f"fork {fmt(fk, 1e6, 'us')} {mb[1]:6.2f} MB  -> fork / plain = {statistics.median(rat):.2f} "
+                        f"({min(rat):.2f}..{max(rat):.2f})")
+                    del arms
+                del fork
+            del parent, plain
+            torch.cuda.empty_cache()
+    say("generate end to end, GPT-2-medium, 4 prompts of 768 tokens x 16 samples, 64 new tokens, sampler=\"fused\", "
+        "step=\"wide\", graph=True (prefill and capture included)")
+    with context.device(dev), torch.no_grad():
+        model = gpt2_medium(dropout=0.0)
+        torch.manual_seed(9)
+        ids = torch.randint(0, model.vocab, (4, 768), device=dev)
+        rep = ids.repeat_interleave(G, 0)
+        kw = dict(temperature=0.8, top_k=40, seed=1, sampler="fused", step="wide")
+        res = rounds_of({"repeated": lambda: model.generate(rep, 64, **kw),
+                         "shared": lambda: model.generate(ids, 64, num_return_sequences=G, **kw)}, rounds, 1)
+        rat = [a / b for a, b in zip(res["shared"], res["repeated"])]
+        say(f"repeated ids {fmt(res['repeated'])}   num_return_sequences={G} {fmt(res['shared'])}  -> shared / repeated "
+            f"= {statistics.median(rat):.3f} ({min(rat):.3f}..{max(rat):.3f})")
+        del model
+    torch.cuda.empty_cache()
+
+
 def section_sampler(dev, rounds):
     say("== 4. token choice in generate(graph=True, temperature=0.8, top_k=40), GPT-2-medium: torch route vs "
         "sampler=\"fused\"")
@@ -607,6 +660,8 @@ def main():
         section_wide(dev, a.rounds)
     if "8" in sec:
         section_kv_fp8(dev, a.rounds)
+    if "9" in sec:
+        section_shared_prefix(dev, a.rounds)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "a" if a.append else "w") as f:
         f.write("\n".join(LINES) + "\n")
