@@ -44,7 +44,8 @@ enum LaunchCounter : int {
   LC_DENSE_WIDE = 16,          // dense_wide.hip, M <= 64 weight-streaming dense
   LC_ATTN_DECODE_FP8 = 17,     // attn_decode_fp8.hip, split-KV single-token attention over an fp8 cache
   LC_ATTN_APPEND_FP8 = 18,     // attention.hip, multi-token append attention over an fp8 cache
-  LC_COUNT = 19
+  LC_DENSE_TALL = 19,          // dense_tall.hip, M <= 256 weight-streaming dense (the split-K sum counts with it)
+  LC_COUNT = 20
 };
 DTF_API long* dtf_launch_counters();  // gemm.hip
 inline void count_launch(int c) { dtf_launch_counters()[c]++; }

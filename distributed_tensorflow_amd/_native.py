@@ -147,6 +147,10 @@ _KERNEL_SIGS = {
     # the M <= 64 weight stream (dense_wide.hip): x, w, bias, out, M, N, K, act, [variant,] stream
     "dtf_dense_wide": [P, P, P, P, I, I, I, I, P],
     "dtf_dense_wide_variant": [P, P, P, P, I, I, I, I, I, P],
+    # the M <= 256 weight stream (dense_tall.hip): x, w, bias, out, slabs, slab_elems, M, N, K, act, [variant,] stream
+    "dtf_dense_tall": [P, P, P, P, P, L, I, I, I, I, P],
+    "dtf_dense_tall_variant": [P, P, P, P, P, L, I, I, I, I, I, P],
+    "dtf_dense_tall_slab_elems": [I, I, I],
     # multi-token append attention over the cache (attention.hip): qkv, k, v, lens, out, B, S, H, Smax, scale, stream
     "dtf_attn_append": [P, P, P, P, P, I, I, I, I, F, P],
     # the fp8 KV cache (attn_decode_fp8.hip, attention.hip): the bf16 entry points' arguments with k_scale, v_scale
@@ -163,7 +167,7 @@ _KERNEL_SIGS = {
 }
 
 
-_RESTYPES = {"dtf_stream_create": P, "dtf_event_create": P}
+_RESTYPES = {"dtf_stream_create": P, "dtf_event_create": P, "dtf_dense_tall_slab_elems": L}
 
 
 class NativeMissing(RuntimeError):

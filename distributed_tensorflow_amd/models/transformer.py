@@ -43,14 +43,14 @@ class _Proj(KL.Layer):
         self.bias = self.add_weight("bias", (self.units,), "zeros")
         self.built = True
 
-    def call(self, x, training=None, link=None, cache=None, fused=None, wide=False):
+    def call(self, x, training=None, link=None, cache=None, fused=None, wide=False, tall=False):
         if cache is not None:
             # inference with a KV cache runs from the bf16 shadow, also for an fp8 model (sampling during training must
             # not touch the fp8 scaling state); the one-token decode step is a weight stream (ops.dense_skinny)
             if fused is not None:  # the fused step: ops.dense_skinny_fused's ln= / residual= / store= options
                 return decode_ops.dense_skinny_fused(x, self.kernel, self.bias, self.activation, **fused)
             if x.shape[-2] == 1:
-                return decode_ops.step_dense(x, self.kernel, self.bias, self.activation, wide=wide)
+                return decode_ops.step_dense(x, self.kernel, self.bias, self.activation, wide=wide, tall=tall)
             return ops.dense(x, self.kernel, self.bias, act=self.activation)
         if self.fp8 and x.is_cuda:
             from ..ops.fp8 import dense_fp8
@@ -77,25 +77,26 @@ class MultiHeadSelfAttention(KL.Layer):
         self.out = _Proj(hidden, fp8=fp8)
 
     def call(self, x, mask=None, training=None, link=None, cache=None, layer=None, append=False, fused=False,
-             ln=None, wide=False):
+             ln=None, wide=False, tall=False):
         if cache is not None:
-            return self._call_cached(x, cache, layer, append, fused, ln, wide)
+            return self._call_cached(x, cache, layer, append, fused, ln, wide, tall)
         o = attn_ops.attention_packed(self.qkv(x, link=link), self.heads, causal=self.causal, mask=mask,
                                       dropout=self.dropout, training=training)
         return self.out(o)
 
-    def _call_cached(self, x, cache, layer, append=False, fused=False, ln=None, wide=False):
+    def _call_cached(self, x, cache, layer, append=False, fused=False, ln=None, wide=False, tall=False):
         """Inference with a KV cache (ops.decode.KVCache): S > 1 is the prefill of an empty cache (the causal
         attention kernel, plus a copy of K and V into the cache), S == 1 a decode step (append, then attend);
         append=True with S > 1 appends the chunk to a filled cache (store at lens + s, then attend_chunk).
         fused=True with S == 1: x is the residual stream and ln the block's first LayerNorm; three launches
         ([LN + QKV + cache store], [attention with its merge], [out-projection + x]) return x + attention.
-        wide=True: the two projections of a decode step with 17 to 64 rows run ops.dense_wide (step_dense)."""
+        wide=True: the two projections of a decode step with 17 to 64 rows run ops.dense_wide (step_dense).
+        tall=True: the same, and with 65 to 256 rows they run ops.dense_tall."""
         if fused and x.shape[1] == 1:
             qkv = self.qkv(x, cache=cache, fused=dict(ln=_ln_args(ln, x), store=(cache, layer)))
             o = cache.attend(layer, qkv, fused=True)
             return self.out(o, cache=cache, fused=dict(residual=x))
-        qkv = self.qkv(x, cache=cache, wide=wide)
+        qkv = self.qkv(x, cache=cache, wide=wide, tall=tall)
         if x.shape[1] == 1:
             cache.store(layer, qkv)
             o = cache.attend(layer, qkv)
@@ -105,7 +106,7 @@ class MultiHeadSelfAttention(KL.Layer):
         else:
             o = attn_ops.attention_packed(qkv, self.heads, causal=True, dropout=0.0, training=False)
             cache.store(layer, qkv)
-        return self.out(o, cache=cache, wide=wide)
+        return self.out(o, cache=cache, wide=wide, tall=tall)
 
 
 class BertLayer(KL.Layer):
@@ -198,14 +199,16 @@ class GPT2Block(KL.Layer):
         self.dropout = dropout
         object.__setattr__(self, "out_into_ln", False)  # set by GPT2: the output's first reader is a LayerNorm
 
-    def call(self, x, training=None, cache=None, layer=None, append=False, fused=False, wide=False):
+    def call(self, x, training=None, cache=None, layer=None, append=False, fused=False, wide=False, tall=False):
         if cache is not None and fused and x.shape[1] == 1:  # the one-token step in five launches
             x = self.att(x, training=False, cache=cache, layer=layer, fused=True, ln=self.ln1)
             h = self.fc(x, cache=cache, fused=dict(ln=_ln_args(self.ln2, x)))
             return self.proj(h, cache=cache, fused=dict(residual=x))
         if cache is not None:  # inference with a KV cache: no dropout, no gradient links
-            x = ops.add(x, self.att(self.ln1(x), training=False, cache=cache, layer=layer, append=append, wide=wide))
-            return ops.add(x, self.proj(self.fc(self.ln2(x), cache=cache, wide=wide), cache=cache, wide=wide))
+            x = ops.add(x, self.att(self.ln1(x), training=False, cache=cache, layer=layer, append=append, wide=wide,
+                                    tall=tall))
+            return ops.add(x, self.proj(self.fc(self.ln2(x), cache=cache, wide=wide, tall=tall), cache=cache,
+                                        wide=wide, tall=tall))
         # the residual gradient of each half-block's input joins its LayerNorm's backward (ResidualGradLink)
         l1, l2 = (ResidualGradLink(), ResidualGradLink()) if (LN_LINK and training and x.is_cuda
                                                               and torch.is_grad_enabled()) else (None, None)
@@ -244,19 +247,19 @@ class GPT2(Model):
         self.dropout = dropout
         self.built = True
 
-    def call(self, ids, training=None, cache=None, append=False, fused=False, wide=False):
+    def call(self, ids, training=None, cache=None, append=False, fused=False, wide=False, tall=False):
         if cache is not None:
-            one = ids.shape[1] == 1  # prefill and append chunks (S > 1) are unchanged by fused= and wide=
-            fused, wide = bool(fused) and one, bool(wide) and one
-            h = self._hidden_cached(ids, cache, append, fused, wide)
-            return self._lm_head(h, decode=one, ln_f=fused, wide=wide)
+            one = ids.shape[1] == 1  # prefill and append chunks (S > 1) are unchanged by fused=, wide= and tall=
+            fused, wide, tall = bool(fused) and one, bool(wide) and one, bool(tall) and one
+            h = self._hidden_cached(ids, cache, append, fused, wide, tall)
+            return self._lm_head(h, decode=one, ln_f=fused, wide=wide, tall=tall)
         x = ops.dropout(ops.embedding(ids, self.wte, self.wpe), self.dropout, training=bool(training))
         for b in self.blocks:
             x = b(x, training=training)
         return ops.dense(self.ln_f(x), self.wte, self.pad_bias)  # tied LM head, logits over vocab_p
 
     # ---- inference with a KV cache (ops.decode)
-    def _hidden_cached(self, ids, cache, append=False, fused=False, wide=False):
+    def _hidden_cached(self, ids, cache, append=False, fused=False, wide=False, tall=False):
         """Final hidden states [B, S, hidden] of an inference forward that fills `cache`: S > 1 prefills an empty
         cache, S == 1 is a decode step at positions cache.lens, and append=True with S > 1 on a cache that is not empty
         appends the chunk at positions cache.lens + s (the caller advances lens afterwards in every case).
@@ -265,7 +268,8 @@ class GPT2(Model):
         rewritten). The default one-token step embeds at cache.lens as it is.
         fused=True (S == 1 only): every block runs its five-launch step and the result is the residual stream before
         ln_f, which _lm_head(ln_f=True) applies as the LM head's prologue.
-        wide=True (S == 1 only): the default step with ops.dense_wide for the projections at 17 to 64 rows."""
+        wide=True (S == 1 only): the default step with ops.dense_wide for the projections at 17 to 64 rows.
+        tall=True (S == 1 only): the wide step, and ops.dense_tall for the projections at 65 to 256 rows."""
         S = ids.shape[1]
         chunk = False
         top = self.cfg["ctx"] - 1
@@ -288,11 +292,13 @@ class GPT2(Model):
             for i, b in enumerate(self.blocks):
                 x = b(x, training=False, cache=cache, layer=i, fused=True)
             return x
-        wide = bool(wide) and S == 1
-        if wide:
+        wide, tall = bool(wide) and S == 1, bool(tall) and S == 1
+        if tall:
+            self._check_tall(ids.shape[0], ids.device)
+        elif wide:
             self._check_wide(ids.shape[0], ids.device)
         for i, b in enumerate(self.blocks):
-            x = b(x, training=False, cache=cache, layer=i, append=chunk, wide=wide)
+            x = b(x, training=False, cache=cache, layer=i, append=chunk, wide=wide, tall=tall)
         return self.ln_f(x)
 
     def _check_fused(self, batch, device):
@@ -327,6 +333,20 @@ class GPT2(Model):
         bad = [s for s in shapes if s[0] % 8 or s[1] % 8]
         if batch > 16 and bad:
             raise ValueError(f"the wide decode step cannot run the projections {bad} (N, K) on dense_wide")
+
+    def _check_tall(self, batch, device):
+        """The tall one-token step: more rows than ops.dense_tall takes, or (past dense_skinny's 16 rows) a projection
+        that neither it nor ops.dense_wide can run, raises here; a shape in WIDE_EXCLUDE / TALL_EXCLUDE stays on
+        ops.dense at the row counts of that kernel."""
+        if torch.device(device).type != "cuda":
+            return
+        if batch > decode_ops.TALL_MAX_ROWS:
+            raise ValueError(f"the tall decode step takes at most {decode_ops.TALL_MAX_ROWS} rows (batch {batch})")
+        hid = self.cfg["hidden"]
+        shapes = [(3 * hid, hid), (hid, hid), (4 * hid, hid), (hid, 4 * hid), (self.vocab_p, hid)]
+        bad = [s for s in shapes if s[0] % 8 or s[1] % 8]
+        if batch > 16 and bad:
+            raise ValueError(f"the tall decode step cannot run the projections {bad} (N, K) on dense_wide / dense_tall")
 
     @staticmethod
     def _refuse_gpu_chunk(ids, cache, n, more):
@@ -397,11 +417,11 @@ class GPT2(Model):
                 cache.advance(valid)
             return self._lm_head(last.reshape(B, 1, -1), decode=True)[:, 0]
 
-    def _lm_head(self, h, decode=False, ln_f=False, wide=False):
+    def _lm_head(self, h, decode=False, ln_f=False, wide=False, tall=False):
         if ln_f:  # the fused step: h is the residual stream, ln_f the LM head's prologue
             return decode_ops.dense_skinny_fused(h, self.wte, self.pad_bias, ln=_ln_args(self.ln_f, h))
         if decode:
-            return decode_ops.step_dense(h, self.wte, self.pad_bias, wide=wide)
+            return decode_ops.step_dense(h, self.wte, self.pad_bias, wide=wide, tall=tall)
         return ops.dense(h, self.wte, self.pad_bias)
 
     def new_cache(self, batch, capacity, device, chunked=False, kv_dtype=None):
@@ -462,6 +482,10 @@ class GPT2(Model):
         step="wide" runs the projections of the one-token step (four a layer and the LM head) on ``ops.dense_wide``, the
         weight stream for 17 to 64 rows, when 16 < batch <= 64; up to 16 rows it is the default step, bit for bit.
         Batch > 64 or a hidden size that is no multiple of 8 raises ValueError before anything is computed.
+        step="tall" is the wide step carried to 256 rows: with 65 to 256 rows (batch, or batch * num_return_sequences)
+        the projections run ``ops.dense_tall`` (x shared through LDS, K split across blocks; the LM head stays on
+        ``ops.dense``, ``ops.decode.TALL_EXCLUDE``); up to 64 rows it is step="wide", bit for bit. More than 256 rows or
+        a hidden size that is no multiple of 8 raises ValueError before anything is computed.
         Default None: the step described above, unchanged (past 16 rows its projections run ``ops.dense``).
 
         kv_dtype="fp8": the cache this call creates (on the plain and the prefill_chunk route) stores K and V as e4m3
@@ -474,7 +498,8 @@ class GPT2(Model):
         the j-th sample of prompt b. The prompt is prefilled once at batch B and its K/V kept once: the cache is
         forked (``KVCache.fork``) and the token loop runs at B * G rows, each decode attention reading the prompt once
         per group (``dtf_attn_decode_shared``) and the row's own new positions behind it. Row b * G + j draws what row
-        b * G + j of ``ids.repeat_interleave(G, 0)`` would draw. Every sampler, graph= and step="wide" apply;
+        b * G + j of ``ids.repeat_interleave(G, 0)`` would draw. Every sampler, graph=, step="wide" and step="tall"
+        apply;
         cache=, prefill_chunk=, step="fused", kv_dtype="fp8" and G > 16 raise ValueError before anything is computed.
         ``last_generation["cache"]`` is the fork (its ``prefix`` the prompt's cache). None or 1: one row per prompt."""
         G = 1 if num_return_sequences is None else int(num_return_sequences)
@@ -483,19 +508,21 @@ class GPT2(Model):
         if G > 1 and (cache is not None or prefill_chunk is not None or step == "fused" or kv_dtype == "fp8"):
             raise ValueError("generate: num_return_sequences > 1 runs on a forked bf16 cache of its own: not with "
                              "cache=, prefill_chunk=, step='fused' or kv_dtype='fp8'")
-        if step not in (None, "fused", "wide"):
-            raise ValueError(f"generate: step {step!r} (None, 'fused' or 'wide')")
+        if step not in (None, "fused", "wide", "tall"):
+            raise ValueError(f"generate: step {step!r} (None, 'fused', 'wide' or 'tall')")
         if kv_dtype not in (None, "bf16", "fp8"):
             raise ValueError(f"generate: kv_dtype {kv_dtype!r} (None, 'bf16' or 'fp8')")
         if cache is not None and kv_dtype is not None and kv_dtype != cache.kv_dtype:
             raise ValueError(f"generate: kv_dtype {kv_dtype!r} against a {cache.kv_dtype} cache")
-        step_fused, step_wide = step == "fused", step == "wide"
+        step_fused, step_wide, step_tall = step == "fused", step == "wide", step == "tall"
         if step_fused and (kv_dtype == "fp8" or (cache is not None and cache.fp8)):
             raise ValueError("generate: step='fused' has no kernels for an fp8 KV cache")
         if step_fused:
             self._check_fused(ids.shape[0], ids.device)
         if step_wide:
             self._check_wide(ids.shape[0] * G, ids.device)
+        if step_tall:
+            self._check_tall(ids.shape[0] * G, ids.device)
         if sampler not in (None, "torch", "fused"):
             raise ValueError(f"generate: sampler {sampler!r} (None, 'torch' or 'fused')")
         if sampler == "torch" and (top_p is not None or repetition_penalty is not None):
@@ -548,8 +575,8 @@ class GPT2(Model):
                 logits = self.extend(ids, cache, plens, prefill_chunk)  # behind what the cache holds, in pieces
 
             def one_token(tok):
-                lg = self._lm_head(self._hidden_cached(tok, cache, fused=step_fused, wide=step_wide), decode=True,
-                                   ln_f=step_fused, wide=step_wide)
+                lg = self._lm_head(self._hidden_cached(tok, cache, fused=step_fused, wide=step_wide, tall=step_tall),
+                                   decode=True, ln_f=step_fused, wide=step_wide, tall=step_tall)
                 cache.advance(1)
                 return lg
 

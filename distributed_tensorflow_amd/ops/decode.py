@@ -28,8 +28,10 @@ sums in a fixed order. bf16 caches and groups of 2 to 16 only; ``attend(fused=Tr
 ``dense_skinny_fused`` and ``KVCache.attend(fused=True)`` are the launches of the fused one-token step
 (``GPT2.generate(step="fused")``): the same kernels with LayerNorm, the residual add, the cache append and the split-KV
 merge inside them. ``dense_wide`` (csrc/kernels/dense_wide.hip) is the weight stream for up to 64 rows, the projections
-of the opt-in wide step (``GPT2.generate(step="wide")``) at 17 to 64 sequences. CPU tensors take the explicit f32 torch
-path.
+of the opt-in wide step (``GPT2.generate(step="wide")``) at 17 to 64 sequences. ``dense_tall``
+(csrc/kernels/dense_tall.hip) carries the weight stream to 256 rows, x shared through LDS and K split across blocks:
+the projections of the tall step (``GPT2.generate(step="tall")``) at 65 to 256 rows, which below that is the wide step.
+CPU tensors take the explicit f32 torch path.
 """
 from __future__ import annotations
 
@@ -315,6 +317,46 @@ def dense_wide(x, w, bias=None, act=None, *, variant=None):
     return out.reshape(*x.shape[:-1], N)
 
 
+TALL_MAX_ROWS = 256
+# (weight rows, x rows, slab budget) of dense_tall_kernel's blocks and split rule, in the order of `variant`
+TALL_VARIANTS = tuple((128, bm, b) for b in (1, 2, 4) for bm in (128, 256, 64))
+
+
+def dense_tall(x, w, bias=None, act=None, *, variant=None):
+    """act(x @ w^T + bias) for at most 256 rows of x (all leading axes together): the weight-streaming kernel of a
+    batched decode step past dense_wide's 64 rows (csrc/kernels/dense_tall.hip). Arguments as dense_skinny's.
+    variant: index into TALL_VARIANTS to run that block shape and split budget instead of the measured choice
+    (tools/bench_generate.py times them all). The split-K scratch is a fresh allocation per call: inside a captured
+    step it lives in the graph's pool, and no later, larger request can free it under a replay."""
+    a = act_code(act)
+    if not on_gpu(x):
+        y = torch.nn.functional.linear(x.to(w.dtype), w, bias)
+        return _act_ref(y, a)
+    w16 = w if w.dtype == BF16 else bf16_shadow(w)
+    w16 = w16.contiguous()
+    x2 = x.reshape(-1, x.shape[-1])
+    x2 = (x2 if x2.dtype == BF16 else x2.to(BF16)).contiguous()
+    if bias is not None and (bias.dtype != F32 or not bias.is_contiguous()):
+        bias = bias.float().contiguous()
+    M, Kd = x2.shape
+    N = w16.shape[0]
+    if w16.shape[1] != Kd:
+        raise ValueError(f"dense_tall: x [..., {Kd}] against w {tuple(w16.shape)}")
+    elems = int(K().dtf_dense_tall_slab_elems(M, N, Kd))
+    if elems < 0:
+        raise RuntimeError(f"dense_tall cannot run x [{M}, {Kd}] against w [{N}, {Kd}] (1 to {TALL_MAX_ROWS} rows, "
+                           "N and K multiples of 8)")
+    slabs = torch.empty(max(elems, 4), dtype=F32, device=x.device)
+    out = torch.empty(M, N, dtype=BF16, device=x.device)
+    if variant is None:
+        call("dtf_dense_tall", ptr(x2), ptr(w16), ptr(bias), ptr(out), ptr(slabs), slabs.numel(), M, N, Kd, a,
+             stream(x.device))
+    else:
+        call("dtf_dense_tall_variant", ptr(x2), ptr(w16), ptr(bias), ptr(out), ptr(slabs), slabs.numel(), M, N, Kd, a,
+             int(variant), stream(x.device))
+    return out.reshape(*x.shape[:-1], N)
+
+
 def ln_max_k():
     """Largest K of dense_skinny_fused's LayerNorm prologue (the kernel's constant: its LDS tile)."""
     return int(K().dtf_dense_skinny_ln_max_k())
@@ -384,16 +426,25 @@ SKINNY_EXCLUDE = frozenset()
 # the same for dense_wide inside the wide step (generate(step="wide")) at 17 to 64 rows. The GPT-2 LM head
 # 1024 -> 50304: 1.08x faster than ops.dense at M = 17, but 0.9x / 0.8x / 0.7x at M = 32 / 48 / 64 (section 7)
 WIDE_EXCLUDE = frozenset({(50304, 1024)})
+# the same for dense_tall inside the tall step (generate(step="tall")) at 65 to 256 rows. The four layer projections
+# are 1.27x to 4.46x faster than ops.dense at M = 65, 128, 192 and 256; the LM head 1024 -> 50304 takes 50 / 56 / 73 /
+# 88 us against 37 to 41 us (0.74x to 0.46x; the best variant 48 / 56 / 64 / 75 us), section 10
+TALL_EXCLUDE = frozenset({(50304, 1024)})
 
 
-def step_dense(x, w, bias=None, act=None, wide=False):
+def step_dense(x, w, bias=None, act=None, wide=False, tall=False):
     """A projection of the one-token decode step: dense_skinny from the bf16 shadow of w wherever it applies.
-    wide=True (the opt-in wide step): with 17 to 64 rows dense_wide instead of ops.dense; up to 16 rows unchanged."""
+    wide=True (the opt-in wide step): with 17 to 64 rows dense_wide instead of ops.dense; up to 16 rows unchanged.
+    tall=True (the opt-in tall step): the wide route up to 64 rows, and with 65 to 256 rows dense_tall."""
     if on_gpu(x):
         M = x.numel() // x.shape[-1]
         N, Kd = w.shape
         if M <= 16 and N % 8 == 0 and Kd % 8 == 0 and (N, Kd) not in SKINNY_EXCLUDE:
             return dense_skinny(x, w, bias, act)
-        if wide and 16 < M <= WIDE_MAX_ROWS and N % 8 == 0 and Kd % 8 == 0 and (N, Kd) not in WIDE_EXCLUDE:
+        if ((wide or tall) and 16 < M <= WIDE_MAX_ROWS and N % 8 == 0 and Kd % 8 == 0
+                and (N, Kd) not in WIDE_EXCLUDE):
             return dense_wide(x, w, bias, act)
+        if (tall and WIDE_MAX_ROWS < M <= TALL_MAX_ROWS and N % 8 == 0 and Kd % 8 == 0
+                and (N, Kd) not in TALL_EXCLUDE):
+            return dense_tall(x, w, bias, act)
     return dense(x, w, bias, act=act)

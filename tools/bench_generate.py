@@ -32,6 +32,9 @@ min..max spread over the rounds is reported; times are host clocks around work t
     against a plain cache of the same B0*G rows, B0 in {1, 4}, prefix 256 and 768, suffix 16 and 64 (as section 2: a
     replayed graph over layers that rotate through HBM), and generate(num_return_sequences=16) against generate on
     ids.repeat_interleave(16, 0) at 4 prompts of 768 tokens.
+10. (--sections 10) past 64 rows: ops.dense_tall, and each variant of its kernel (block shape x slab budget), against
+    ops.dense at M = 65, 128, 192, 256 on the same shapes (as section 7), and the captured one-token step at B = 128
+    and 256, context ~350 and ~1000, default against tall=True (generate(step="tall")).
 """
 import argparse
 import os
@@ -486,6 +489,87 @@ def section_shared_prefix(dev, rounds):
     torch.cuda.empty_cache()
 
 
+def section_tall(dev, rounds):
+    say("== 10. ops.dense_tall vs ops.dense at 65 to 256 rows, GPT-2-medium projections (K -> N), weights rotating "
+        "through HBM; every variant (weight rows x x rows, slab budget b) of the kernel, `tall` is the one "
+        "dtf_dense_tall launches")
+    from distributed_tensorflow_amd.ops.decode import TALL_VARIANTS, dense_tall
+    not_faster = []
+    with torch.no_grad():
+        for K, N in ((1024, 3072), (1024, 1024), (1024, 4096), (4096, 1024), (1024, 50304)):
+            wbytes = N * K * 2
+            copies = max(2, min(64, (512 << 20) // wbytes))
+            ws = [torch.randn(N, K, device=dev) * 0.02 for _ in range(copies)]
+            bias = torch.zeros(N, device=dev)
+            for w in ws:
+                ops._util.bf16_shadow(w)
+            for M in (65, 128, 192, 256):
+                x = torch.randn(M, K, device=dev).to(torch.bfloat16)
+
+                def arm(variant):
+                    return graph_of(lambda: [dense_tall(x, w, bias, variant=variant) for w in ws])
+
+                arms = {"dense": graph_of(lambda: [ops.dense(x, w, bias) for w in ws]), "tall": arm(None)}
+                arms.update({f"v{v}": arm(v) for v in range(len(TALL_VARIANTS))})
+                res = {k: [t / copies for t in ts] for k, ts in rounds_of(arms, rounds, 10).items()}
+                de, ta = res["dense"], res["tall"]
+                bw = wbytes / statistics.median(ta)
+                # faster only by more than the baseline's own spread: the slowest tall round under the fastest dense one
+                verdict = "" if max(ta) < min(de) else "   <-- NOT FASTER than ops.dense beyond the spread"
+                if verdict:
+                    not_faster.append((K, N, M))
+                say(f"{K:5d}->{N:5d} M={M:3d} ({copies:2d} copies): tall {fmt(ta, 1e6, 'us')} "
+                    f"[{bw / 1e12:.2f} TB/s, {100 * bw / COPY_BW:.0f}% of copy bw]   dense {fmt(de, 1e6, 'us')}   "
+                    f"x{statistics.median(de) / statistics.median(ta):.2f}{verdict}")
+                for lo in range(0, len(TALL_VARIANTS), 3):
+                    say("        " + "   ".join(f"({bn}x{bm:3d},b{b}) {fmt(res[f'v{v}'], 1e6, 'us')}"
+                                                for v, (bn, bm, b) in list(enumerate(TALL_VARIANTS))[lo:lo + 3]))
+                del arms
+            del ws
+            torch.cuda.empty_cache()
+    say("shapes where dense_tall is not faster than ops.dense (these belong in ops.decode.TALL_EXCLUDE): "
+        + (", ".join(f"{k}->{n} at M={m}" for k, n, m in not_faster) if not_faster else "none"))
+    say("per token: the captured one-token step of GPT-2-medium, default (projections on ops.dense past 16 rows) "
+        "against tall=True, alternating inside each round")
+    with context.device(dev), torch.no_grad():
+        model = gpt2_medium(dropout=0.0)
+        for B in (128, 256):
+            for L in (384, 1024):
+                S0, steps = L - 32, 24
+                torch.manual_seed(B * 10000 + L)
+                tok = torch.randint(0, model.vocab, (B, 1), device=dev)
+                cache = model.new_cache(B, L, dev)
+                _fill(cache, S0)
+
+                def stepper(tall):
+                    def step(t):
+                        lg = model(t, training=False, cache=cache, tall=tall)
+                        cache.advance(1)
+                        return lg
+                    cap = CapturedStep(step, split=False)
+                    for _ in range(4):
+                        cap(tok)
+                    assert cap.captured
+
+                    def go():
+                        cache.lens.fill_(S0)  # stay at context S0 .. S0 + steps
+                        for _ in range(steps):
+                            cap(tok)
+                    return go
+
+                r = rounds_of({"default": stepper(False), "tall": stepper(True)}, rounds, 1)
+                de = [t / steps for t in r["default"]]
+                ta = [t / steps for t in r["tall"]]
+                rat = [a / b for a, b in zip(ta, de)]
+                say(f"B={B} context {S0}..{S0 + steps}: step captured {fmt(de)} /token   tall {fmt(ta)} /token  -> "
+                    f"tall / default = {statistics.median(rat):.3f} ({min(rat):.3f}..{max(rat):.3f}); the default "
+                    f"step's rounds spread {min(de) / statistics.median(de):.3f}..{max(de) / statistics.median(de):.3f} "
+                    "of their median")
+                del cache
+        del model
+    torch.cuda.empty_cache()
+
+
 def section_sampler(dev, rounds):
     say("== 4. token choice in generate(graph=True, temperature=0.8, top_k=40), GPT-2-medium: torch route vs "
         "sampler=\"fused\"")
@@ -662,6 +746,8 @@ def main():
         section_kv_fp8(dev, a.rounds)
     if "9" in sec:
         section_shared_prefix(dev, a.rounds)
+    if "10" in sec:
+        section_tall(dev, a.rounds)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "a" if a.append else "w") as f:
         f.write("\n".join(LINES) + "\n")
