@@ -186,11 +186,16 @@ __global__ void __launch_bounds__(AD_WAVES * 64) attn_shared_prefix_kernel(
   }
 }
 
-// attn_decode_part_kernel's stream over keys max(P, chunk*128) .. min(lim, chunk*128 + 127) of the row's own cache
+// attn_decode_part_kernel's stream over keys max(P, chunk*128) .. min(lim, chunk*128 + 127) of the row's own cache.
+// BEAM (dtf_attn_decode_beam): the key and value of position p are those of physical row (b / G) * G + slots[b, p] of
+// the own cache, slots [B0*G, Smax] uint8, except position lens[b] (the token dtf_kv_store has just put there), which
+// is row b's own. A lane fetches the table byte of each of its four keys (at the clamped position, and clamped to
+// G - 1: the address stays inside the group's rows whatever the table holds), then issues all eight loads as before.
+template <bool BEAM>
 __global__ void __launch_bounds__(AD_WAVES * 64) attn_shared_suffix_kernel(
     const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc,
     const long* __restrict__ plens, const long* __restrict__ lens, float* __restrict__ part0, int G, int H,
-    int Smax_prefix, int Smax, int nchunks, float scale) {
+    int Smax_prefix, int Smax, int nchunks, float scale, const unsigned char* __restrict__ slots) {
   __shared__ float sm[AD_WAVES][AD_PART];
   const int bh = blockIdx.x, chunk = blockIdx.y;
   const int b = bh / H, h = bh - b * H;
@@ -203,12 +208,32 @@ __global__ void __launch_bounds__(AD_WAVES * 64) attn_shared_suffix_kernel(
   const bf16_t* vb = vc + (long)bh * Smax * 64 + c * 8;
   const int kw = k0 + wave * 32 + g;
   uint4 kr[4], vr[4];
+  if (BEAM) {
+    const long own = lens[b];
+    const int r0 = b / G * G;
+    int slot[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int key = kw + j * 8;
-    const long row = key < Smax ? key : Smax - 1;
-    kr[j] = *reinterpret_cast<const uint4*>(kb + row * 64);
-    vr[j] = *reinterpret_cast<const uint4*>(vb + row * 64);
+    for (int j = 0; j < 4; ++j) {
+      const int key = kw + j * 8;
+      slot[j] = slots[(long)b * Smax + (key < Smax ? key : Smax - 1)];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int key = kw + j * 8;
+      const long row = key < Smax ? key : Smax - 1;
+      const int src = row == own ? b : r0 + (slot[j] < G ? slot[j] : G - 1);
+      const long at = (((long)src * H + h) * Smax + row) * 64 + c * 8;
+      kr[j] = *reinterpret_cast<const uint4*>(kc + at);
+      vr[j] = *reinterpret_cast<const uint4*>(vc + at);
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int key = kw + j * 8;
+      const long row = key < Smax ? key : Smax - 1;
+      kr[j] = *reinterpret_cast<const uint4*>(kb + row * 64);
+      vr[j] = *reinterpret_cast<const uint4*>(vb + row * 64);
+    }
   }
   float q[8];
   load8(qkv + (long)b * 3 * H * 64 + h * 64 + c * 8, q);
@@ -314,14 +339,10 @@ __global__ void __launch_bounds__(64) attn_shared_merge_kernel(const float* __re
   out[(long)bh * 64 + d] = f2bf(a / l);  // position lim is a suffix key: l > 0
 }
 
-}  // namespace
-
-// One query row per (b, h) from qkv [B0*G, 1, 3*H*64]; k_prefix / v_prefix [B0, H, Smax_prefix, 64] shared by the G rows
-// of a group up to plens[B0], k_own / v_own [B0*G, H, Smax_own, 64] behind it up to lens[B0*G]; out [B0*G, 1, H*64]
-// bf16; scratch: B0*G*H*2*ceil(Smax_own/chunk)*66 f32.
-DTF_API int dtf_attn_decode_shared(const void* qkv, const void* k_prefix, const void* v_prefix, const void* k_own,
-                                   const void* v_own, const long* plens, const long* lens, void* out, float* scratch,
-                                   int B0, int G, int H, int Smax_prefix, int Smax_own, float scale, void* stream) {
+// slots: null (every row reads its own cache) or the beam table of the suffix pass
+int launch_shared(const void* qkv, const void* k_prefix, const void* v_prefix, const void* k_own, const void* v_own,
+                  const long* plens, const long* lens, void* out, float* scratch, int B0, int G, int H,
+                  int Smax_prefix, int Smax_own, float scale, const unsigned char* slots, void* stream) {
   if (!qkv || !k_prefix || !v_prefix || !k_own || !v_own || !plens || !lens || !out || !scratch) return -1;
   if (B0 < 1 || G < 2 || G > 16 || H < 1 || Smax_prefix < 1 || Smax_own < 1) return -1;
   if (!aligned16(qkv) || !aligned16(k_prefix) || !aligned16(v_prefix) || !aligned16(k_own) || !aligned16(v_own))
@@ -334,10 +355,40 @@ DTF_API int dtf_attn_decode_shared(const void* qkv, const void* k_prefix, const 
   hipLaunchKernelGGL(attn_shared_prefix_kernel, dim3(B0 * H, nchunks), dim3(AD_WAVES * 64), 0, st, (const bf16_t*)qkv,
                      (const bf16_t*)k_prefix, (const bf16_t*)v_prefix, plens, lens, scratch, G, H, Smax_prefix,
                      Smax_own, nchunks, scale);
-  hipLaunchKernelGGL(attn_shared_suffix_kernel, dim3(B * H, nchunks), dim3(AD_WAVES * 64), 0, st, (const bf16_t*)qkv,
-                     (const bf16_t*)k_own, (const bf16_t*)v_own, plens, lens, scratch + half, G, H, Smax_prefix,
-                     Smax_own, nchunks, scale);
+  if (slots)
+    hipLaunchKernelGGL(attn_shared_suffix_kernel<true>, dim3(B * H, nchunks), dim3(AD_WAVES * 64), 0, st,
+                       (const bf16_t*)qkv, (const bf16_t*)k_own, (const bf16_t*)v_own, plens, lens, scratch + half, G,
+                       H, Smax_prefix, Smax_own, nchunks, scale, slots);
+  else
+    hipLaunchKernelGGL(attn_shared_suffix_kernel<false>, dim3(B * H, nchunks), dim3(AD_WAVES * 64), 0, st,
+                       (const bf16_t*)qkv, (const bf16_t*)k_own, (const bf16_t*)v_own, plens, lens, scratch + half, G,
+                       H, Smax_prefix, Smax_own, nchunks, scale, slots);
   hipLaunchKernelGGL(attn_shared_merge_kernel, dim3(B * H), dim3(64), 0, st, (const float*)scratch, plens, lens,
                      (bf16_t*)out, G, H, Smax_prefix, Smax_own, nchunks, half);
   return (int)hipGetLastError();
+}
+
+}  // namespace
+
+// One query row per (b, h) from qkv [B0*G, 1, 3*H*64]; k_prefix / v_prefix [B0, H, Smax_prefix, 64] shared by the G rows
+// of a group up to plens[B0], k_own / v_own [B0*G, H, Smax_own, 64] behind it up to lens[B0*G]; out [B0*G, 1, H*64]
+// bf16; scratch: B0*G*H*2*ceil(Smax_own/chunk)*66 f32.
+DTF_API int dtf_attn_decode_shared(const void* qkv, const void* k_prefix, const void* v_prefix, const void* k_own,
+                                   const void* v_own, const long* plens, const long* lens, void* out, float* scratch,
+                                   int B0, int G, int H, int Smax_prefix, int Smax_own, float scale, void* stream) {
+  return launch_shared(qkv, k_prefix, v_prefix, k_own, v_own, plens, lens, out, scratch, B0, G, H, Smax_prefix,
+                       Smax_own, scale, nullptr, stream);
+}
+
+// The same for beams: slots [B0*G, Smax_own] uint8 names, per row and own position, the physical row of the group
+// (0 .. G-1) whose k_own / v_own hold that position; position lens[b] is always row b's own.
+DTF_API int dtf_attn_decode_beam(const void* qkv, const void* k_prefix, const void* v_prefix, const void* k_own,
+                                 const void* v_own, const long* plens, const long* lens, const void* slots, void* out,
+                                 float* scratch, int B0, int G, int H, int Smax_prefix, int Smax_own, float scale,
+                                 void* stream) {
+  if (!slots) return -1;
+  const int rc = launch_shared(qkv, k_prefix, v_prefix, k_own, v_own, plens, lens, out, scratch, B0, G, H,
+                               Smax_prefix, Smax_own, scale, (const unsigned char*)slots, stream);
+  if (rc == 0) count_launch(LC_ATTN_DECODE_BEAM);
+  return rc;
 }

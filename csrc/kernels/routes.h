@@ -45,7 +45,9 @@ enum LaunchCounter : int {
   LC_ATTN_DECODE_FP8 = 17,     // attn_decode_fp8.hip, split-KV single-token attention over an fp8 cache
   LC_ATTN_APPEND_FP8 = 18,     // attention.hip, multi-token append attention over an fp8 cache
   LC_DENSE_TALL = 19,          // dense_tall.hip, M <= 256 weight-streaming dense (the split-K sum counts with it)
-  LC_COUNT = 20
+  LC_BEAM_SELECT = 20,         // beam.hip, the beam selector (both stages count as one)
+  LC_ATTN_DECODE_BEAM = 21,    // attn_decode_shared.hip, shared-prefix attention with the slot-indirect suffix pass
+  LC_COUNT = 22
 };
 DTF_API long* dtf_launch_counters();  // gemm.hip
 inline void count_launch(int c) { dtf_launch_counters()[c]++; }

@@ -37,7 +37,8 @@ RUNTIME_SO = os.path.join(LIBDIR, "libdtf_runtime.so")
 # before are not listed: their build, and with it their code, stays what it was.
 _NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"attn_decode_fused.hip": _NO_PACKED_F32, "dense_wide.hip": _NO_PACKED_F32,
-               "attn_decode_fp8.hip": _NO_PACKED_F32, "attn_decode_shared.hip": _NO_PACKED_F32, "dense_tall.hip": _NO_PACKED_F32}
+               "attn_decode_fp8.hip": _NO_PACKED_F32, "attn_decode_shared.hip": _NO_PACKED_F32, "dense_tall.hip": _NO_PACKED_F32,
+               "beam.hip": _NO_PACKED_F32}
 
 
 def _hipcc() -> str:

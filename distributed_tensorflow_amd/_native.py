@@ -161,6 +161,12 @@ _KERNEL_SIGS = {
     # shared-prefix decode attention (attn_decode_shared.hip): qkv, k_prefix, v_prefix, k_own, v_own, plens, lens, out,
     # scratch, B0, G, H, Smax_prefix, Smax_own, scale, stream
     "dtf_attn_decode_shared": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, P],
+    # the same with the beam table of the suffix pass: ..., plens, lens, slots, out, scratch, ...
+    "dtf_attn_decode_beam": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, P],
+    # beam search (beam.hip): logits, f32, ld, B0, G, n, scores, done, eos, pad, parent, token, scratch, stream
+    "dtf_beam_select": [P, I, L, I, I, I, P, P, L, L, P, P, P, P],
+    # slots, hist, parent, lens, token, B0, G, cap, width, stream
+    "dtf_beam_reorder": [P, P, P, P, P, I, I, I, L, P],
     # fused token sampler (sample.hip): logits, f32, ld, B, n, 1/T, greedy, top_k, P, r, 1/r, seed, uniform, table, out,
     # width, pos, done, eos, pad, tok_out, stream
     "dtf_sample_logits": [P, I, L, I, I, F, I, I, I, F, F, U, P, P, P, L, P, P, L, L, P, P],

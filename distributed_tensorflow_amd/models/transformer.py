@@ -447,7 +447,8 @@ class GPT2(Model):
 
     def generate(self, ids, max_new_tokens, *, prompt_lens=None, temperature=0.0, top_k=None, seed=None,
                  eos_token_id=None, pad_token_id=None, graph=True, cache=None, prefill_chunk=None, top_p=None,
-                 repetition_penalty=None, sampler=None, step=None, kv_dtype=None, num_return_sequences=None):
+                 repetition_penalty=None, sampler=None, step=None, kv_dtype=None, num_return_sequences=None,
+                 num_beams=None):
         """Continue `ids` [B, S0] by max_new_tokens tokens with a KV cache -> int64 [B, S0 + max_new_tokens].
 
         cache: a KVCache to continue (``last_generation["cache"]`` of an earlier call, or one filled through
@@ -501,8 +502,37 @@ class GPT2(Model):
         b * G + j of ``ids.repeat_interleave(G, 0)`` would draw. Every sampler, graph=, step="wide" and step="tall"
         apply;
         cache=, prefill_chunk=, step="fused", kv_dtype="fp8" and G > 16 raise ValueError before anything is computed.
-        ``last_generation["cache"]`` is the fork (its ``prefix`` the prompt's cache). None or 1: one row per prompt."""
+        ``last_generation["cache"]`` is the fork (its ``prefix`` the prompt's cache). None or 1: one row per prompt.
+
+        num_beams=G (2..16): beam search -> [B, S0 + max_new_tokens], each prompt's best beam (pad after eos). The
+        prompt is prefilled once at batch B and the cache forked with ``beams=True``; a step is ``ops.beam_select`` (the
+        G best of the group's G * vocab continuations by summed log-probability, finished beams frozen in the beam),
+        ``KVCache.reorder`` (the slot table and the token history follow the chosen parents; no K/V is copied) and the
+        model step on the chosen tokens, whose attention reads each beam's own positions through the slot table
+        (``dtf_attn_decode_beam``). With graph=True the three are one captured step. No length penalty and no early
+        stopping. ``last_generation`` also holds ``"beams"`` [B * G, S0 + max_new_tokens] and ``"beam_scores"``
+        [B * G], descending within each prompt's group. step="wide" and step="tall" apply on B * G rows. temperature,
+        top_k, top_p, repetition_penalty, sampler, num_return_sequences, cache=, prefill_chunk=, step="fused",
+        kv_dtype="fp8", G outside 2..16 and a vocabulary above 65536 raise ValueError before anything is computed."""
+        if num_beams is not None:
+            other = dict(temperature=temperature or None, top_k=top_k, top_p=top_p, sampler=sampler, cache=cache,
+                         repetition_penalty=repetition_penalty, prefill_chunk=prefill_chunk,
+                         num_return_sequences=None if num_return_sequences in (None, 1) else num_return_sequences,
+                         step="fused" if step == "fused" else None, kv_dtype="fp8" if kv_dtype == "fp8" else None)
+            bad = ", ".join(f"{k}={v!r}" if k in ("step", "kv_dtype") else k
+                            for k, v in sorted(other.items()) if v is not None)
+            if bad:
+                raise ValueError(f"generate: num_beams runs on a forked bf16 cache of its own and ranks by summed "
+                                 f"log-probability: not with {bad}")
+            if not 2 <= int(num_beams) <= 16:
+                raise ValueError(f"generate: num_beams {num_beams} (2..16)")
+            if self.vocab > 65536:
+                raise ValueError(f"generate: num_beams takes a vocabulary of at most 65536 (got {self.vocab})")
+            if not 0 <= int(pad_token_id if pad_token_id is not None else (eos_token_id or 0)) < 65536:
+                raise ValueError("generate: num_beams takes a pad token id in [0, 65536)")
         G = 1 if num_return_sequences is None else int(num_return_sequences)
+        if num_beams is not None:
+            G = int(num_beams)
         if G < 1 or G > 16:
             raise ValueError(f"generate: num_return_sequences {num_return_sequences} (1..16)")
         if G > 1 and (cache is not None or prefill_chunk is not None or step == "fused" or kv_dtype == "fp8"):
@@ -547,7 +577,7 @@ class GPT2(Model):
                 raise ValueError(f"cached tokens ({held}) + new tokens ({S0}) + max_new_tokens ({n_new}) exceed "
                                  f"min(cache capacity {cache.capacity}, context length {ctx})")
         if n_new == 0 and cache is None:
-            return ids.repeat_interleave(G, 0) if G > 1 else ids.clone()
+            return ids.repeat_interleave(G, 0) if G > 1 and num_beams is None else ids.clone()
         pad = pad_token_id if pad_token_id is not None else (eos_token_id if eos_token_id is not None else 0)
         gen = None
         if temperature and not fused:
@@ -566,7 +596,7 @@ class GPT2(Model):
                 last = ops.gather_rows(h.reshape(B * S0, -1), rows)  # each row's own last prompt position
                 logits = self._lm_head(last.reshape(B, 1, -1), decode=True)[:, 0]
                 if G > 1:  # G rows per prompt from here on; the prompt's K/V stay where they are
-                    cache = cache.fork(G)
+                    cache = cache.fork(G, beams=num_beams is not None)
                     ids, plens, logits = (t.repeat_interleave(G, 0) for t in (ids, plens, logits))
                     B *= G
             else:
@@ -584,6 +614,27 @@ class GPT2(Model):
             out = torch.full((B, S0 + n_new), int(pad), dtype=torch.int64, device=dev)
             out[:, :S0] = torch.where(col < plens[:, None], ids, out[:, :S0])
             done = torch.zeros(B, dtype=torch.bool, device=dev)
+            if num_beams is not None:
+                # as the fused sampler's step: `logits` is read and rewritten in place, a replay takes no argument
+                logits = logits.contiguous().clone()
+                scores = torch.tensor([0.0] + [float("-inf")] * (G - 1), device=dev).repeat(B // G)
+
+                def beam_step(_):
+                    parent, tok = ops.beam_select(logits, n=self.vocab, scores=scores, done=done, group=G,
+                                                  eos=eos_token_id, pad=int(pad))
+                    cache.reorder(parent, history=out, token=tok)  # the new token lands in column cache.lens
+                    logits.copy_(one_token(tok[:, None])[:, 0])
+                    return logits
+
+                captured = None
+                if graph and dev.type == "cuda":
+                    from ..graphs import CapturedStep
+                    captured = CapturedStep(beam_step, split=False)
+                for t in range(n_new):
+                    (captured or beam_step)(())
+                object.__setattr__(self, "last_generation", {"cache": cache, "logits": logits.clone(), "step": captured,
+                                                             "beams": out, "beam_scores": scores})
+                return out[::G].clone()
             if fused:
                 # the step reads `logits` and rewrites it in place, so a replay takes no argument and copies nothing in
                 logits = logits.contiguous().clone()

@@ -9,3 +9,4 @@ from .optim import optim_apply  # noqa: F401
 from .mha import attention, attention_packed  # noqa: F401
 from .decode import KVCache, dense_skinny, dense_skinny_fused, dense_tall, dense_wide  # noqa: F401
 from .sample import sample_logits, sample_reference  # noqa: F401
+from .beam import beam_select, beam_select_reference  # noqa: F401

@@ -530,7 +530,7 @@ def call_log():
 LAUNCH_COUNTERS = ("w4_256", "w4_128", "gemm256", "gemm_tile", "gemm_dact", "beta_bf16", "splitk", "w4f8_256", "w4f8_128",
                    "gemm256_fp8", "attn_decode", "dense_skinny", "sample", "attn_append",
                    "dense_skinny_fused", "attn_decode_fused", "dense_wide", "attn_decode_fp8", "attn_append_fp8",
-                   "dense_tall")
+                   "dense_tall", "beam_select", "attn_decode_beam")
 
 
 def launch_counts():

@@ -23,6 +23,10 @@ batch B0 * G and K/V of its own for the new tokens only, and keeps the filled pa
 ``attend`` (csrc/kernels/attn_decode_shared.hip) reads the prompt's keys and values once per group, the G queries
 against a key tile on the MFMA, and each row's own positions with the split-KV pass; both write partials that one merge
 sums in a fixed order. bf16 caches and groups of 2 to 16 only; ``attend(fused=True)`` and multi-token chunks raise.
+``fork(G, beams=True)`` is the cache of beam search (``GPT2.generate(num_beams=G)``): a uint8 slot table names, per row
+and own position, the physical row of the group that holds it, the split-KV pass resolves every key through it
+(``dtf_attn_decode_beam``), and ``reorder(parent)`` lets row j continue row parent[j] by rewriting table columns in place
+(``dtf_beam_reorder``, csrc/kernels/beam.hip): no K/V is ever copied.
 
 ``dense_skinny`` is an explicit route: ``ops.dense`` / ``ops.gemm`` dispatch as before and never reach it.
 ``dense_skinny_fused`` and ``KVCache.attend(fused=True)`` are the launches of the fused one-token step
@@ -102,15 +106,23 @@ class KVCache:
             self.counters = torch.zeros(self.batch * self.heads, dtype=torch.int32, device=self.device)
         # set by fork(): group > 1 marks a forked cache; on the GPU prefix is the parent and plens its lengths
         self.group, self.prefix, self.plens = 1, None, None
+        # fork(beams=True): rows may continue each other's history (reorder); on the GPU through the slot table
+        self.beams, self.slots = False, None
 
-    def fork(self, group):
+    def fork(self, group, beams=False):
         """A cache of batch B0 * group for `group` continuations of every row of this (filled, bf16) cache: row
         b0 * group + j continues row b0. Same capacity, layers and heads. On the GPU nothing is copied: the new cache
         has uninitialised K/V of its own for positions from plens = lens.clone() on and keeps this cache by reference
         as its read-only `prefix`; `attend` reads positions below plens[b0] once per group from the prefix
         (dtf_attn_decode_shared). Do not write to the parent while a fork is in use. On the CPU the parent's rows are
         repeated into a plain f32 cache: the reference semantics. ValueError for an empty, fp8 or already forked cache
-        and for a group outside 2..16."""
+        and for a group outside 2..16.
+
+        beams=True (beam search, GPT2.generate(num_beams=)): the rows of a group may continue each other's history
+        (`reorder`). On the GPU the fork also owns `slots`, uint8 [B0 * group, capacity]: row b's key and value at an
+        own position p (plens <= p < lens[b]) live in physical row (b // group) * group + slots[b, p] of the fork's
+        K/V; position lens[b], the token `store` has just put there, is always row b's own. Every entry of row b
+        starts as b % group, and `attend` resolves each key through the table (dtf_attn_decode_beam)."""
         G = int(group)
         if not 2 <= G <= 16:
             raise ValueError(f"KVCache.fork: group {group} (2..16)")
@@ -128,7 +140,42 @@ class KVCache:
             c.scratch = torch.empty(2 * c.scratch.numel(), dtype=F32, device=self.device)  # a prefix and a suffix half
         else:
             c.k, c.v = self.k.repeat_interleave(G, 1), self.v.repeat_interleave(G, 1)
+        c.beams = bool(beams)
+        if c.beams and c.prefix is not None:
+            own = torch.arange(c.batch, device=self.device) % G
+            c.slots = own.to(torch.uint8)[:, None].repeat(1, c.capacity)
         return c
+
+    def reorder(self, parent, history=None, token=None):
+        """Row g * G + j of a fork(beams=True) continues row g * G + parent[g * G + j] (parent [batch] int32, values
+        0 .. G-1; the rows of a group hold the same length). Call it after the step that stored position lens - 1 and
+        before the next `store`. On the GPU no K/V moves: one launch (dtf_beam_reorder) gathers the slot table by
+        parent column by column, in place, and makes the column just closed (lens - 1) parent itself. history
+        [batch, width] int64 (each row's tokens so far) is gathered the same way in the same launch, and its column
+        lens[b] receives token [batch] int64 when given. CPU tensors: an index_select of K/V and of the history."""
+        if not self.beams:
+            raise ValueError("KVCache.reorder: not a fork(beams=True)")
+        G = self.group
+        if tuple(parent.shape) != (self.batch,) or parent.dtype != torch.int32 or not parent.is_contiguous():
+            raise ValueError(f"KVCache.reorder: parent is a contiguous int32 [{self.batch}]")
+        if history is not None and (history.dim() != 2 or history.shape[0] != self.batch
+                                    or history.dtype != torch.int64 or not history.is_contiguous()):
+            raise ValueError(f"KVCache.reorder: history is a contiguous int64 [{self.batch}, width]")
+        if token is not None and (history is None or tuple(token.shape) != (self.batch,)
+                                  or token.dtype != torch.int64 or not token.is_contiguous()):
+            raise ValueError(f"KVCache.reorder: token is a contiguous int64 [{self.batch}] and goes with a history")
+        if self.slots is not None:
+            call("dtf_beam_reorder", ptr(self.slots), ptr(history), ptr(parent), ptr(self.lens), ptr(token),
+                 self.batch // G, G, self.capacity, 0 if history is None else history.shape[1],
+                 stream(self.device))
+            return
+        rows = torch.arange(self.batch) // G * G + parent.long().clamp(0, G - 1)
+        self.k, self.v = self.k.index_select(1, rows), self.v.index_select(1, rows)
+        if history is not None:
+            history.copy_(history.index_select(0, rows))
+            if token is not None:
+                at = self.lens < history.shape[1]
+                history[torch.nonzero(at)[:, 0], self.lens[at]] = token[at]
 
     def _check(self, layer, qkv, S=None):
         B, s, T = qkv.shape
@@ -181,6 +228,12 @@ class KVCache:
             out = torch.empty(B, 1, HD, dtype=BF16, device=qkv.device)
             if self.prefix is not None:  # a fork: positions below plens come from the parent, once per group
                 pre = self.prefix
+                if self.slots is not None:  # beams: the own positions through the slot table
+                    call("dtf_attn_decode_beam", ptr(q), ptr(pre.k[layer]), ptr(pre.v[layer]), ptr(self.k[layer]),
+                         ptr(self.v[layer]), ptr(self.plens), ptr(self.lens), ptr(self.slots), ptr(out),
+                         ptr(self.scratch), pre.batch, self.group, self.heads, pre.capacity, self.capacity, scale,
+                         stream(qkv.device))
+                    return out
                 call("dtf_attn_decode_shared", ptr(q), ptr(pre.k[layer]), ptr(pre.v[layer]), ptr(self.k[layer]),
                      ptr(self.v[layer]), ptr(self.plens), ptr(self.lens), ptr(out), ptr(self.scratch), pre.batch,
                      self.group, self.heads, pre.capacity, self.capacity, scale, stream(qkv.device))

@@ -35,6 +35,10 @@ min..max spread over the rounds is reported; times are host clocks around work t
 10. (--sections 10) past 64 rows: ops.dense_tall, and each variant of its kernel (block shape x slab budget), against
     ops.dense at M = 65, 128, 192, 256 on the same shapes (as section 7), and the captured one-token step at B = 128
     and 256, context ~350 and ~1000, default against tall=True (generate(step="tall")).
+11. (--sections 11) beam search: ops.beam_select + KVCache.reorder against torch log_softmax + topk + index_select of
+    24 layers' own K/V at B0 in {1, 4}, G in {4, 16} and the GPT-2 vocabulary; KVCache.attend on fork(beams=True)
+    against the plain fork at the shapes of section 9; and generate(num_beams=16) against
+    generate(num_return_sequences=16) at 4 prompts of 768 tokens.
 """
 import argparse
 import os
@@ -489,6 +493,91 @@ def section_shared_prefix(dev, rounds):
     torch.cuda.empty_cache()
 
 
+def section_beam(dev, rounds):
+    say("== 11. beam search (generate(num_beams=G)): ops.beam_select + KVCache.reorder, the slot-indirect attention, "
+        "and the captured step")
+    H, cap, n, ld, own = 16, 1024, 50257, 50304, 64
+    say(f"token choice alone, vocabulary {n} (ld {ld}, bf16 logits ~ N(0, 4^2)), inside a replayed graph: beam_select + "
+        f"reorder (slot table [B, {cap}] and history [B, {cap}]) against torch log_softmax + topk + index_select of 24 "
+        f"layers' own K/V ({own} positions, H = {H})")
+    with torch.no_grad():
+        for B0 in (1, 4):
+            for G in (4, 16):
+                B = B0 * G
+                base = ops.KVCache(1, B0, 1, cap, dev)
+                base.empty = False
+                base.lens.fill_(768)
+                fork = base.fork(G, beams=True)
+                fork.lens.fill_(768 + own)
+                logits = (4 * torch.randn(B, ld, device=dev)).to(torch.bfloat16)
+                scores = -torch.rand(B, device=dev)
+                done = torch.zeros(B, dtype=torch.bool, device=dev)
+                hist = torch.zeros(B, cap, dtype=torch.int64, device=dev)
+                kv = torch.randn(2, 24, B, H, own, 64, device=dev).to(torch.bfloat16)
+                rows0 = (torch.arange(B, device=dev) // G * G)
+
+                def kernels():
+                    parent, tok = ops.beam_select(logits, n=n, scores=scores.clone(), done=done, group=G, pad=0)
+                    fork.reorder(parent, history=hist, token=tok)
+
+                def torch_route():
+                    val = scores[:, None] + torch.log_softmax(logits.float()[:, :n], -1)
+                    top = val.view(B0, G * n).topk(G, -1).indices.view(-1)
+                    rows = rows0 + top // n
+                    return kv.index_select(2, rows), hist.index_select(0, rows), top % n
+
+                res = rounds_of({"kernels": graph_of(kernels), "torch": graph_of(torch_route)}, rounds, 50)
+                rat = [a / b for a, b in zip(res["kernels"], res["torch"])]
+                say(f"B0={B0} x G={G}: beam_select + reorder {fmt(res['kernels'], 1e6, 'us')}   torch "
+                    f"{fmt(res['torch'], 1e6, 'us')}  -> kernels / torch = {statistics.median(rat):.3f} "
+                    f"({min(rat):.3f}..{max(rat):.3f})")
+                del kv
+        G = 16
+        say(f"KVCache.attend alone, G = {G}, H = {H}, capacity {cap}, as section 9: fork(beams=True) with a random slot "
+            "table against the plain fork")
+        for B0 in (1, 4):
+            B = B0 * G
+            layers = max(2, min(16, -(-(537 << 20) // (2 * B * H * cap * 128))))
+            parent = ops.KVCache(layers, B0, H, cap, dev)
+            qkv = torch.randn(B, 1, 3 * H * 64, device=dev).to(torch.bfloat16)
+            for Lp in (256, 768):
+                _fill(parent, Lp)
+                plain, beam = parent.fork(G), parent.fork(G, beams=True)
+                plain.k.normal_()
+                plain.v.normal_()
+                beam.k, beam.v = plain.k, plain.v
+                beam.slots = torch.randint(0, G, (B, cap), device=dev).to(torch.uint8)
+                for Ls in (16, 64):
+                    plain.lens.fill_(Lp + Ls - 1)
+                    beam.lens.fill_(Lp + Ls - 1)
+                    arms = {"plain": graph_of(lambda: [plain.attend(l, qkv) for l in range(layers)]),
+                            "beam": graph_of(lambda: [beam.attend(l, qkv) for l in range(layers)])}
+                    res = rounds_of(arms, rounds, 20)
+                    pl, bm = ([t / layers for t in res[k]] for k in ("plain", "beam"))
+                    rat = [a / b for a, b in zip(bm, pl)]
+                    say(f"B0={B0} x G={G} prefix {Lp} suffix {Ls}: plain fork {fmt(pl, 1e6, 'us')}   beams "
+                        f"{fmt(bm, 1e6, 'us')}  -> beams / plain = {statistics.median(rat):.2f} "
+                        f"({min(rat):.2f}..{max(rat):.2f})")
+                    del arms
+                del plain, beam
+            del parent
+            torch.cuda.empty_cache()
+    say("generate end to end, GPT-2-medium, 4 prompts of 768 tokens x 16 rows, 64 new tokens, step=\"wide\", graph=True "
+        "(prefill and capture included): num_beams=16 against num_return_sequences=16 with sampler=\"fused\"")
+    with context.device(dev), torch.no_grad():
+        model = gpt2_medium(dropout=0.0)
+        torch.manual_seed(9)
+        ids = torch.randint(0, model.vocab, (4, 768), device=dev)
+        res = rounds_of({"samples": lambda: model.generate(ids, 64, num_return_sequences=G, temperature=0.8, top_k=40,
+                                                            seed=1, sampler="fused", step="wide"),
+                         "beams": lambda: model.generate(ids, 64, num_beams=G, step="wide")}, rounds, 1)
+        rat = [a / b for a, b in zip(res["beams"], res["samples"])]
+        say(f"num_return_sequences={G} {fmt(res['samples'])}   num_beams={G} {fmt(res['beams'])}  -> beams / samples "
+            f"= {statistics.median(rat):.3f} ({min(rat):.3f}..{max(rat):.3f})")
+        del model
+    torch.cuda.empty_cache()
+
+
 def section_tall(dev, rounds):
     say("== 10. ops.dense_tall vs ops.dense at 65 to 256 rows, GPT-2-medium projections (K -> N), weights rotating "
         "through HBM; every variant (weight rows x x rows, slab budget b) of the kernel, `tall` is the one "
@@ -748,6 +837,8 @@ def main():
         section_shared_prefix(dev, a.rounds)
     if "10" in sec:
         section_tall(dev, a.rounds)
+    if "11" in sec:
+        section_beam(dev, a.rounds)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "a" if a.append else "w") as f:
         f.write("\n".join(LINES) + "\n")
